@@ -1,7 +1,15 @@
 """Benchmark: Mrays/s of the MI355X ray tracer on BASELINE.json's config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps of `value`'s frame loop, write its outputs (--dump-outputs) and
+print the line.  Everything else described below and in DESIGN.md section 6
+-- the app's host path, per-kernel durations and the roofline, the long
+in-flight window, the RGBA8 Texture leg, the frame against the committed
+fixture, the CPU baseline, and at N>1 every phase beyond the assemblies --
+is measured with --full.
 
 Workload (BASELINE config 3, the headline): one 4096x4096 frame, 256
 spheres + 64 cubes, dense synthetic scene (seed 3, k =
@@ -23,7 +31,7 @@ bit-exactly against a one-GPU render of the whole frame on rank 0):
                    rt_shared_open) and each rank's trace kernel stores its
                    band straight into it over xGMI; a one-element RCCL
                    all-reduce after the render tells rank 0 all bands landed.
-Also reported at N>1: the render/assembly split, the RGBA8 Texture form of
+Also reported at N>1 with --full: the render/assembly split, the RGBA8 Texture form of
 the same assembly (4 B/ray, the north_star's Texture), BASELINE config 4
 (8192^2, 192 + 64, seed 4) with the same assembly, and weak scaling (each
 rank renders a 4096x4096 band of a 4096 x 4096N frame, no assembly) as a
@@ -62,6 +70,16 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the "
+                         "app's host path, per-kernel durations and the roofline, the "
+                         "--sustained window, the RGBA8 Texture leg, the frame against the "
+                         "committed fixture, the CPU baseline; at N>1 the render/assembly "
+                         "split, the roofline, the one-GPU baseline and the extras")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame that the last timed step of "
+                         "`value`'s loop produced to DIR/frame.npy (float64; frames of more "
+                         "than 2^20 pixels as a fixed, seeded sample of 2^20 pixels)")
     ap.add_argument("--warmup-ms", type=float, default=50.0,
                     help="the untimed warmup also runs until this much wall time of GPU load "
                          "has passed (the clock ramps up over tens of milliseconds)")
@@ -139,6 +157,15 @@ def parse(argv=None):
     ap.add_argument("--selftest-cpu", action="store_true",
                     help=argparse.SUPPRESS)  # tests: the N>1 plumbing on gloo, no GPU
     return ap.parse_args(argv)
+
+
+def plain_run(args):
+    """Without --full only the headline figure is measured: the options that
+    choose among the other measurements are switched off."""
+    if not args.full:
+        args.no_cpu_baseline = args.no_host_path = args.no_extras = True
+        args.sustained = 0
+    return args
 
 
 # The ONE JSON line goes to the process's original stdout; everything else
@@ -566,14 +593,17 @@ def inflight_step(pkg, c: Ctx, ds, w, h, fmt, path, slots: int):
     def step():
         fns[n[0] % slots]()
         n[0] += 1
+    step.count = n  # steps run so far: step i renders into frames[i % slots]
     return step, frames, (rts, streams)
 
 
-def measure_inflight(args, c: Ctx, pkg, ds, w, h, fmt, ref_frame, slots=None, ramp_step=None):
+def measure_inflight(args, c: Ctx, pkg, ds, w, h, fmt, ref_frame, slots=None, ramp_step=None,
+                     last=None):
     """Throughput with `slots` (default args.inflight) frames in flight (the
     N=1 `value`): the timed region is K whole frames, every one a full prep +
     bin + trace pass; each slot's frame is compared with the one-stream
-    frame."""
+    frame.  `last`: a list that receives the frame the last timed step
+    rendered (--dump-outputs)."""
     slots = slots or args.inflight
     step, frames, keep = inflight_step(pkg, c, ds, w, h, fmt, args.path, slots)
     for _ in range(4 * slots + args.warmup):
@@ -588,6 +618,8 @@ def measure_inflight(args, c: Ctx, pkg, ds, w, h, fmt, ref_frame, slots=None, ra
     # the trace kernel's duration, not stretched by overlap.
     ramp = c.clock_ramp(ramp_step or step, args.warmup_ms)
     ms = c.timed(step, args.steps)
+    if last is not None:
+        last.append(sample_frame(frames[(step.count[0] - 1) % slots]))
     out = {"frames_in_flight": slots, "ms_per_step": round(ms, 4),
            "value": round(mrays_per_s(w * h, ms), 1), "clock_ramp_steps": ramp}
     if getattr(args, "sustained", 0) > 0:
@@ -629,6 +661,35 @@ def device_scene(pkg, c: Ctx, width, height, spheres, cubes, seed, k):
 def frame_tensor(c: Ctx, rows, width, fmt):
     shape = (rows, width, 4) if fmt == "i32x4" else (rows, width)
     return c.torch.empty(shape, dtype=c.torch.int32, device=c.dev)
+
+
+DUMP_PIXELS = 1 << 20  # --dump-outputs: at most this many pixels (32 MiB as float64 int32x4)
+DUMP_SEED = 20240607
+
+
+def sample_frame(frame) -> np.ndarray:
+    """--dump-outputs: the frame (a device or host int32 tensor, rows x width
+    [x 4]) as float64, whole when it has at most DUMP_PIXELS pixels, else the
+    pixels at DUMP_PIXELS flat positions drawn once from a fixed seed (the
+    same positions, in rising order, for every run of the same frame size).
+    Every int32 is exact in float64."""
+    import torch
+
+    px = frame.reshape(frame.shape[0] * frame.shape[1], -1)
+    if px.shape[0] > DUMP_PIXELS:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], DUMP_PIXELS,
+                                                              replace=False))
+        px = px.index_select(0, torch.from_numpy(pos).to(px.device))
+        return px.cpu().numpy().astype(np.float64).reshape((DUMP_PIXELS,) + tuple(frame.shape[2:]))
+    return px.cpu().numpy().astype(np.float64).reshape(tuple(frame.shape))
+
+
+def write_outputs(directory, arrays: dict):
+    """--dump-outputs: one DIR/<name>.npy per array."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
 
 
 # ---------------------------------------------------------------------------
@@ -733,21 +794,31 @@ def run_single(args, c: Ctx, pkg):
     # frames in flight stretch each trace by ~8 %, so the pass runs first).
     # Not the timed region itself: with the events attached the wall time per
     # step grows by 25-40%, while the kernels' own durations agree with
-    # rocprofv3's.
-    rt.profile(True)
-    for _ in range(args.steps):  # untimed: grows the event pool to K renders
-        step()
-    c.sync()
-    rt.profile_read()
-    rt.profile(True)
-    prof_wall_ms = c.timed(step, args.steps)
-    prof = rt.profile_read()
-    rt.profile(False)
+    # rocprofv3's.  (--full only.)
+    prof = None
+    if args.full:
+        rt.profile(True)
+        for _ in range(args.steps):  # untimed: grows the event pool to K renders
+            step()
+        c.sync()
+        rt.profile_read()
+        rt.profile(True)
+        prof_wall_ms = c.timed(step, args.steps)
+        prof = rt.profile_read()
+        rt.profile(False)
+    # --dump-outputs: the one-stream loop's frame (with --full the profiled
+    # pass has rendered it again since, with the same bound step) and, below,
+    # the frame of the in-flight loop's last timed step; the loop that gives
+    # `value` decides which is written
+    dump = args.dump_outputs is not None
+    one_stream_frame = sample_frame(out) if dump else None
+    inflight_frame = [] if dump else None
     # The timed region of `value`: K frames with args.inflight in flight
     # (a frame loop's throughput; 1 = the one-stream number above)
     inflight = None
     if args.inflight > 1 and args.trace_mode == 0:
-        inflight = measure_inflight(args, c, pkg, ds, w, h, args.format, out, ramp_step=step)
+        inflight = measure_inflight(args, c, pkg, ds, w, h, args.format, out, ramp_step=step,
+                                    last=inflight_frame)
     # `value`: the faster frame loop.  Frames in flight win at config 3; on
     # frames of 1 GiB and more two traces at once write the HBM less
     # efficiently than one after the other, and the one-stream loop wins
@@ -755,13 +826,43 @@ def run_single(args, c: Ctx, pkg):
     value_ms = (inflight["ms_per_step"]
                 if inflight and inflight["frame_check"] == "bit-exact"
                 and inflight["ms_per_step"] < wall_ms else wall_ms)
+    if dump:
+        write_outputs(args.dump_outputs, {
+            "frame": inflight_frame[0] if value_ms != wall_ms else one_stream_frame})
+
+    rays = w * h
+    algo_bytes = BYTES_PER_RAY[args.format] * rays
+    workload = CONFIG_NAMES.get((w, h, args.spheres, args.cubes), "custom")
+    line = {
+        "metric": METRIC, "value": round(mrays_per_s(rays, value_ms), 1), "unit": "Mrays/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(value_ms, 4),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+        "data": "synthetic", "full": bool(args.full),
+        "config": {"workload": f"{workload}: {w}x{h} frame, {args.spheres} spheres + "
+                               f"{args.cubes} cubes, dense k={k:.2f}, seed {args.seed}",
+                   "width": w, "height": h, "spheres": args.spheres, "cubes": args.cubes,
+                   "format": args.format,
+                   "parallelism": "1 GPU (the whole frame)" + (
+                       f", {args.inflight} frames in flight (one stream, context and frame "
+                       f"buffer each)" if value_ms != wall_ms else ", one stream")},
+        "frames_in_flight": inflight,
+        "one_stream": {"ms_per_step": round(wall_ms, 4),
+                       "value": round(mrays_per_s(rays, wall_ms), 1),
+                       "event_ms_per_step": round(event_ms, 4)},
+        "event_ms_per_step": round(event_ms, 4),
+        "clock_ramp": {"ms": args.warmup_ms, "untimed_steps": ramp_steps},
+    }
+    if args.dump_outputs is not None:
+        line["dump_outputs"] = {"frame": "frames_in_flight" if value_ms != wall_ms
+                                else "one_stream"}
+    if not args.full:  # a plain run ends here
+        rt.close()
+        return line
 
     kernel = rt.last_kernel()  # the kernel the library actually ran
     n = max(prof["renders"], 1)
     trace_ms, prep_ms, bin_ms = prof["trace_ms"] / n, prof["prep_ms"] / n, prof["bin_ms"] / n
 
-    rays = w * h
-    algo_bytes = BYTES_PER_RAY[args.format] * rays
     achieved = algo_bytes / (trace_ms * 1e-3) / 1e9
     traffic = None
     pmc_path = Path(args.pmc)
@@ -879,26 +980,10 @@ def run_single(args, c: Ctx, pkg):
     # timed region; the in-flight slots' frames were compared with this one)
     ref = frame_check_ref(pkg, out, scene, w, h, args.format, args.golden)
     cpu = None if args.no_cpu_baseline else cpu_baseline(args, scene, w, h)
-    workload = CONFIG_NAMES.get((w, h, args.spheres, args.cubes), "custom")
     rt.close()
-    return {
-        "metric": METRIC, "value": round(mrays_per_s(rays, value_ms), 1), "unit": "Mrays/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(value_ms, 4),
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": f"{workload}: {w}x{h} frame, {args.spheres} spheres + "
-                               f"{args.cubes} cubes, dense k={k:.2f}, seed {args.seed}",
-                   "width": w, "height": h, "spheres": args.spheres, "cubes": args.cubes,
-                   "format": args.format,
-                   "parallelism": "1 GPU (the whole frame)" + (
-                       f", {args.inflight} frames in flight (one stream, context and frame "
-                       f"buffer each)" if value_ms != wall_ms else ", one stream")},
-        "frames_in_flight": inflight,
+    line.update({
         "frame_check_ref": ref.pop("frame_check_ref"),
         "frame_check_ref_source": ref,
-        "one_stream": {"ms_per_step": round(wall_ms, 4),
-                       "value": round(mrays_per_s(rays, wall_ms), 1),
-                       "event_ms_per_step": round(event_ms, 4)},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": traffic, "kernel": kernel, "kernel_ms": round(trace_ms, 4),
@@ -907,13 +992,12 @@ def run_single(args, c: Ctx, pkg):
                      # the frame level: the same bytes over ms_per_step (what
                      # `value` measures: prep + binning + trace, frames in flight)
                      "frame_frac": round(algo_bytes / (value_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-        "event_ms_per_step": round(event_ms, 4),
         "profiled_pass_ms_per_step": round(prof_wall_ms, 4),
-        "clock_ramp": {"ms": args.warmup_ms, "untimed_steps": ramp_steps},
         "texture_rgba8": texture,
         "cpu_baseline": cpu,
         "host_path": host,
-    }
+    })
+    return line
 
 
 def cpu_baseline(args, scene, w, h):
@@ -1099,7 +1183,7 @@ def _wrap_device(c: Ctx, ptr: int, rows, width, fmt):
 
 
 def measure_assembly(args, c, pkg, rt, ds, width, height, fmt, how, split=False, bands=None,
-                     name=None, scene=None):
+                     name=None, scene=None, dumps=None):
     if failing(args, c, name or how):
         raise RuntimeError(f"--fail-assembly {args.fail_assembly}")
     a = Assembly(c, pkg, rt, ds, width, height, fmt, how, bands=bands)
@@ -1117,6 +1201,9 @@ def measure_assembly(args, c, pkg, rt, ds, width, height, fmt, how, split=False,
         c.clock_ramp(ramp_step, args.warmup_ms)
     c.sync()
     ms = c.timed(a.step, args.steps)
+    if dumps is not None and a.root:  # --dump-outputs: the last timed step's frame
+        c.sync()
+        dumps[name or how] = sample_frame(a.frame)
     rb0, re0 = a.bands[0]
     res = {"ms_per_step": round(ms, 4),
            "mrays": round(mrays_per_s(width * height, ms), 1),
@@ -1259,7 +1346,8 @@ def device_scene_from(c: Ctx, scene):
     return t, ds
 
 
-def measure_assemblies(args, c, pkg, rt, ds, w, h, fmt, phases, res, split=False, scene=None):
+def measure_assemblies(args, c, pkg, rt, ds, w, h, fmt, phases, res, split=False, scene=None,
+                       dumps=None):
     """The frame assembled on rank 0 three ways: equal bands by RCCL
     point-to-point, equal bands by xGMI peer stores, and cost-balanced bands
     by xGMI peer stores.  The equal split makes every other rank wait on its
@@ -1273,7 +1361,8 @@ def measure_assemblies(args, c, pkg, rt, ds, w, h, fmt, phases, res, split=False
 
     for how in ("rccl_p2p", "xgmi_peer_store"):
         phases.run(how, lambda how=how: measure_assembly(args, c, pkg, rt, ds, w, h, fmt, how,
-                                                         split=split, scene=scene), res)
+                                                         split=split, scene=scene,
+                                                         dumps=dumps), res)
 
     def balanced():
         costs = calibrate_peer_store(args, c, pkg, rt, ds, w, h, fmt)
@@ -1282,7 +1371,8 @@ def measure_assemblies(args, c, pkg, rt, ds, w, h, fmt, phases, res, split=False
                                                   "shared mapping)"}
         bal = rowbands.balanced_bands(h, costs)
         r = measure_assembly(args, c, pkg, rt, ds, w, h, fmt, "xgmi_peer_store", split=split,
-                             bands=bal, name="xgmi_peer_store_balanced", scene=scene)
+                             bands=bal, name="xgmi_peer_store_balanced", scene=scene,
+                             dumps=dumps)
         r["cost_model_us"] = [{"fixed": round(a * 1e6, 2), "per_row": round(s * 1e6, 4)}
                               for a, s in costs]
         return r
@@ -1304,6 +1394,7 @@ def multi_line(args, c: Ctx, state: dict) -> dict:
         "unit": "Mrays/s", "n_gpus": c.world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(ms, 4) if ms else None, "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "full": bool(getattr(args, "full", False)),
         "config": {"workload": f"{workload}: {w}x{h} frame, {args.spheres} spheres + "
                                f"{args.cubes} cubes, dense k={k:.2f}, seed {args.seed}",
                    "width": w, "height": h, "spheres": args.spheres, "cubes": args.cubes,
@@ -1411,8 +1502,16 @@ def run_multi(args, c: Ctx, pkg):
         return EXIT_NO_VALUE
     rt, ds, scene = env["rt"], env["ds"], env["scene"]
 
+    # (--full: each assembly's render / assembly split as well)
+    dumps = {} if args.dump_outputs is not None else None
     measure_assemblies(args, c, pkg, rt, ds, w, h, args.format, phases, state["assembly"],
-                       split=True, scene=scene)
+                       split=args.full, scene=scene, dumps=dumps)
+    if dumps is not None and c.rank == 0:
+        # --dump-outputs: the assembled frame of `value`'s assembly (rank 0)
+        best = pick_value(state["assembly"])[0]
+        if best in dumps:
+            write_outputs(args.dump_outputs, {"frame": dumps[best]})
+    dumps = None
 
     def roofline():
         # the trace kernel on this rank's band, local stores (the roofline of
@@ -1435,7 +1534,8 @@ def run_multi(args, c: Ctx, pkg):
                 "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
                 "kernel": kernel, "kernel_ms": round(trace_ms, 4),
                 "algo_bytes_per_launch": band_bytes, "scope": "rank 0's band, local stores"}
-    phases.run("roofline", roofline, state)
+    if args.full:
+        phases.run("roofline", roofline, state)
 
     def one_gpu():
         # t(N=1) in the same run, the baseline of scaling_assembled and
@@ -1454,7 +1554,8 @@ def run_multi(args, c: Ctx, pkg):
         return {"ms_per_step": round(ms, 4), "mrays": round(mrays_per_s(w * h, ms), 1),
                 "scope": "rank 0 alone renders the whole frame into its own HBM (one stream), "
                          "same run"}
-    phases.run("one_gpu", one_gpu, state)
+    if args.full:
+        phases.run("one_gpu", one_gpu, state)
 
     if not args.no_extras:
         # the Texture (RGBA8, MainState.cpp:1023-1037) assembled the same way
@@ -1686,6 +1787,7 @@ def main():
     claim_stdout()
     if args.selftest_cpu:
         sys.exit(run_selftest_cpu(args))
+    plain_run(args)
     c = Ctx(args)
     pkg = __graft_entry__.load_package()
     if c.distributed:

@@ -6,7 +6,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$R"; mkdir -p gpurun_out; export TMPDIR=/tmp
 TAG=${TAG:-mix}
 export RT_HIP_LIBRARY=${LIB:-$R/opencl-ray-tracer_amd/librt_hip.so}
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-host-path ${EXTRA:-}"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-host-path ${EXTRA:-}"
 i=0
 for grp in "SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT64" \
            "SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU" \

@@ -614,3 +614,34 @@ def test_sustained_window_is_a_fixed_frame_count():
     a = b.parse([])
     assert a.sustained >= 500  # default on, independent of --steps
     assert b.parse(["--sustained", "0"]).sustained == 0
+
+
+def test_plain_run_switches_the_other_measurements_off():
+    """Without --full only the headline is measured; --full leaves every
+    option as given.  --steps is the timed step count either way."""
+    b = _bench()
+    a = b.plain_run(b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"]))
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_host_path and a.no_extras and a.sustained == 0
+    f = b.plain_run(b.parse(["--full", "--steps", "7"]))
+    assert f.full and f.steps == 7 and f.sustained >= 500
+    assert not (f.no_cpu_baseline or f.no_host_path or f.no_extras)
+
+
+def test_dump_outputs_sample_is_fixed(tmp_path):
+    """--dump-outputs: a frame of at most DUMP_PIXELS pixels is written whole,
+    a larger one as the pixels at DUMP_PIXELS positions that depend on the
+    frame size alone, as float64 (exact for every int32), under 64 MB."""
+    import torch
+    b = _bench()
+    small = torch.arange(-30, 30, dtype=torch.int32).reshape(3, 5, 4)
+    assert np.array_equal(b.sample_frame(small), small.numpy().astype(np.float64))
+    h, w = 1100, 1000
+    big = (torch.arange(h * w, dtype=torch.int32) - 2 ** 31 + 7).reshape(h, w)  # an rgba8 frame
+    one, two = b.sample_frame(big), b.sample_frame(big.clone())
+    assert one.dtype == np.float64 and one.shape == (b.DUMP_PIXELS,) and np.array_equal(one, two)
+    pos = (one + 2 ** 31 - 7).astype(np.int64)
+    assert np.all(np.diff(pos) > 0) and pos[0] >= 0 and pos[-1] < h * w
+    assert b.DUMP_PIXELS * 4 * 8 <= 64 << 20  # int32x4: four values per pixel
+    b.write_outputs(tmp_path / "a" / "b", {"frame": one})
+    assert np.array_equal(np.load(tmp_path / "a" / "b" / "frame.npy"), one)

@@ -161,7 +161,7 @@ def test_bench_rehearsal_assemblies(world, tmp_path):
     the strong-scaling fields."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
            f"--nproc-per-node={world}", "--master-addr=127.0.0.1", "--master-port=29533",
-           str(REPO / "bench.py"), "--gpus", str(world), "--rehearse", "--steps", "3",
+           str(REPO / "bench.py"), "--gpus", str(world), "--rehearse", "--full", "--steps", "3",
            "--warmup", "1", "--width", "1024", "--height", "512"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=tmp_path)
@@ -209,8 +209,8 @@ def test_bench_rehearsal_without_launcher(tmp_path):
     bench.py starts its two ranks itself (both on cuda:0 in this rehearsal,
     gloo), exactly one line comes out with n_gpus 2, bit-exact assemblies and
     the scaling keys, and the status is 0."""
-    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--rehearse", "--steps", "3",
-           "--warmup", "1", "--width", "1024", "--height", "512", "--no-extras",
+    cmd = [sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--rehearse", "--full",
+           "--steps", "3", "--warmup", "1", "--width", "1024", "--height", "512", "--no-extras",
            "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=_no_launcher_env(),
                        cwd=tmp_path)
@@ -613,3 +613,73 @@ def test_randomized_parity_sweep(pkg, rt, oracle, seed):
     if fmt == "rgba8":
         want = oracle.pack_rgba8(want)
     assert np.array_equal(got, want), (seed, w, h, ns, nc, k, rows, fmt, knobs)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("rt_bench", REPO / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+@pytest.mark.parametrize("case", ["whole", "sampled", "one_stream", "full"])
+def test_bench_plain_run_and_dump_outputs(pkg, oracle, tmp_path, case):
+    """A plain N=1 run (in this process: parse -> plain_run -> run_single)
+    times --steps frames and measures nothing beside the headline: the line
+    has the result keys and none of the --full ones.  --dump-outputs writes
+    the last timed step's frame as float64: the whole frame when it has at
+    most 2^20 pixels ("whole": 333x257), else the pixels at the fixed seeded
+    positions ("sampled": 1200x900), equal to the oracle's frame either way;
+    "one_stream": the one-stream loop as `value`'s loop (--inflight 1).
+    "full": the same command with --full carries the other measurements and
+    dumps the same frame."""
+    torch = pytest.importorskip("torch")
+    b = _bench_module()
+    w, h = (1200, 900) if case == "sampled" else (333, 257)
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--warmup-ms", "1",
+            "--width", str(w), "--height", str(h), "--spheres", "40", "--cubes", "10",
+            "--seed", "31", "--dump-outputs", str(tmp_path / "out")]
+    if case == "one_stream":
+        argv += ["--inflight", "1"]
+    if case == "full":
+        argv += ["--full", "--cpu-threads", "2", "--app-calls", "2", "--sustained", "8"]
+    args = b.plain_run(b.parse(argv))
+    before = torch.cuda.current_stream()
+    try:
+        line = b.run_single(args, b.Ctx(args), pkg)
+    finally:
+        torch.cuda.synchronize()
+        torch.cuda.set_stream(before)
+    line = json.loads(json.dumps(line))
+    assert line["steps"] == 3 and line["n_gpus"] == 1 and line["unit"] == "Mrays/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["value"] == pytest.approx(w * h / (line["ms_per_step"] * 1e-3) / 1e6, rel=2e-2)
+    loops = [line["one_stream"]["ms_per_step"]]
+    if case != "one_stream":
+        assert line["frames_in_flight"]["frame_check"] == "bit-exact"
+        loops.append(line["frames_in_flight"]["ms_per_step"])
+    else:
+        assert line["frames_in_flight"] is None and line["dump_outputs"]["frame"] == "one_stream"
+    assert line["ms_per_step"] == pytest.approx(min(loops), abs=1e-4)
+    full_keys = {"roofline", "host_path", "cpu_baseline", "texture_rgba8", "frame_check_ref",
+                 "profiled_pass_ms_per_step"}
+    if case == "full":
+        assert line["full"] is True and full_keys <= set(line)
+        assert line["roofline"]["kernel_ms"] > 0 and line["cpu_baseline"]["value"] > 0
+        assert line["frames_in_flight"]["sustained"]["steps"] == 8
+        assert line["texture_rgba8"]["frames_in_flight"]["frame_check"] == "bit-exact"
+    else:
+        assert line["full"] is False and not (full_keys & set(line))
+        assert "sustained" not in (line["frames_in_flight"] or {})
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == ["frame.npy"]
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float64 and got.nbytes <= 64 << 20
+    scene = pkg.Scene.synthetic(w, h, 40, 10, seed=31, k=w / 640.0)
+    want = oracle.trace(scene, w, h, threads=THREADS).astype(np.float64)
+    if case == "sampled":
+        pos = np.sort(np.random.default_rng(b.DUMP_SEED).choice(w * h, b.DUMP_PIXELS,
+                                                                replace=False))
+        want = want.reshape(w * h, 4)[pos]
+    assert got.shape == want.shape and np.array_equal(got, want)
