@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, SURVEY_FNV, golden_scene, load_golden, probe_fnv
+from test_gpu_numeric_edges import PATHS, render_all_paths
 
 pytestmark = pytest.mark.gpu
 
@@ -205,18 +206,15 @@ EDGE_CASES = {
 @pytest.mark.parametrize("case", sorted(EDGE_CASES))
 @pytest.mark.parametrize("size", [(101, 77), (1, 1), (64, 64)])
 def test_edge_cases(pkg, rt, oracle, case, size):
+    """Every edge scene through every kernel of the path matrix
+    (test_gpu_numeric_edges.PATHS: generic, both small-scene kernels,
+    trace3_kernel with and without the forced depth culls, the split trace,
+    trace_bin_kernel, the wide tile build) in both formats, the kernel that
+    ran asserted, each frame the oracle's bit for bit."""
     w, h = size
     scene = _scene_from(pkg, **EDGE_CASES[case])
-    want = oracle.trace(scene, w, h)
-    try:
-        # binned: the small-scene kernel (<= 512 primitives), then the general
-        # prep -> coarse -> trace path on the same scene
-        for path, small in (("binned", True), ("binned", False), ("generic", True)):
-            rt.set_small_path(small)
-            got, _ = rt.render(scene, w, h, path=path)
-            assert not diff_report(got, want), f"{path}/{small}: {diff_report(got, want)}"
-    finally:
-        rt.set_small_path(True)
+    n = render_all_paths(rt, oracle, scene, w, h, label=f"{case} {w}x{h}")
+    assert n == 2 * len(PATHS)
 
 
 def test_nonfinite_scene_falls_back_exactly(pkg, rt, oracle):
