@@ -23,6 +23,18 @@ int check_args(const rt_scene* s, int32_t width, int32_t height, int32_t row_beg
 int check_reserve(int32_t width, int32_t rows, int32_t num_spheres, int32_t num_cubes,
                   int32_t fmt);
 
+/* Is `fmt` one of the output formats (RT_FORMAT_*; 2 is reserved)? */
+constexpr bool format_ok(int32_t fmt) {
+    return fmt == RT_FORMAT_I32X4 || fmt == RT_FORMAT_RGBA8 || fmt == RT_FORMAT_HIT;
+}
+
+/* Bytes of one pixel of a valid `fmt`: 16 (I32X4), 4 (RGBA8) or 8 (HIT).
+ * constexpr: the kernels' store widths and the host's sizes are one rule. */
+constexpr size_t pixel_bytes(int32_t fmt) {
+    return fmt == RT_FORMAT_I32X4 ? 16u : fmt == RT_FORMAT_HIT ? sizeof(rt_hit) : 4u;
+}
+static_assert(sizeof(rt_hit) == 8, "rt_hit layout");
+
 /* Bytes of `rows` rows of a width-pixel frame in `fmt`. */
 size_t frame_bytes(int32_t width, int32_t rows, int32_t fmt);
 

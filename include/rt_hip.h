@@ -18,6 +18,9 @@
  *   RT_FORMAT_RGBA8: uint32[rows][width], (uint8)r | (uint8)g<<8 |
  *                    (uint8)b<<16 | 0xFF<<24  (the Texture packing,
  *                    MainState.cpp:984-994, :1023-1037)
+ *   RT_FORMAT_HIT:   rt_hit[rows][width], what `collide` found before it
+ *                    shades (MainState.cpp:330-394): the float `closest` and
+ *                    the winning object (see rt_hit below)
  */
 #ifndef RT_HIP_H
 #define RT_HIP_H
@@ -42,7 +45,25 @@ enum {
     RT_ERR_UNSUPPORTED = -5
 };
 
-enum { RT_FORMAT_I32X4 = 0, RT_FORMAT_RGBA8 = 1 };
+/* Output formats.  Value 2 is reserved and stays RT_ERR_INVALID_ARG. */
+enum { RT_FORMAT_I32X4 = 0, RT_FORMAT_RGBA8 = 1, RT_FORMAT_HIT = 3 };
+
+/* One pixel of an RT_FORMAT_HIT frame (8 bytes).
+ *   t       the reference's `closest` after the whole collide loop
+ *           (MainState.cpp:330-394), the exact float: nothing is normalised
+ *           or clamped, a negative t or -inf is stored as it is.
+ *   object  the colour slot of the winner: cube c gives c, sphere i gives
+ *           num_cubes + i (cubes are tested first, MainState.cpp:347-392).
+ * A miss is t = 300000.0f (the loop's initial `closest`, MainState.cpp:345)
+ * and object = -1.  The comparison is a strict `<`, so no hit carries
+ * t == 300000: object == -1 exactly when t == 300000, which is also the
+ * miss test of the shade (MainState.cpp:398).  Of several candidates with
+ * the same float t the first in the reference's order wins (lower cube,
+ * lower triangle, cubes before spheres, lower sphere). */
+typedef struct rt_hit {
+    float t;
+    int32_t object;
+} rt_hit;
 
 /* Kernel path selection (rt_render*, `path` field of rt_timing). */
 enum {
@@ -139,9 +160,10 @@ const char* rt_error_string(int status);
  *                 frame; only rows [row_begin, row_end) are uploaded, and
  *                 origins that are bit for bit that grid are recognised on
  *                 the device and keep the binned path)
- *   host_out      int32[4*width*rows] (I32X4) or uint32[width*rows] (RGBA8)
+ *   host_out      int32[4*width*rows] (I32X4), uint32[width*rows] (RGBA8)
+ *                 or rt_hit[width*rows] (HIT)
  *   timing        may be NULL
- * Empty scenes are legal (all pixels (0,0,0,255)). */
+ * Empty scenes are legal (all pixels (0,0,0,255); HIT: all {300000, -1}). */
 int rt_render(rt_ctx* ctx, const rt_scene* scene, const float ray_dir[4],
               const float* ray_origins, int32_t width, int32_t height,
               int32_t row_begin, int32_t row_end, int32_t out_format,
@@ -176,7 +198,9 @@ int rt_render_multi(rt_ctx* const* ctxs, int32_t num_ctx, const rt_scene* scene,
  * Asynchronous: work is enqueued on `stream` and the call returns.
  * Renders on one context share its workspace (primitive records, candidate
  * lists): enqueue them on one stream, or synchronise before switching
- * streams.  Concurrent renders need one context each. */
+ * streams.  Concurrent renders need one context each.
+ * `device_out` must be aligned to the pixel: 16 bytes for I32X4, 4 for RGBA8,
+ * 8 for HIT (one 8-byte store per pixel). */
 int rt_render_device(rt_ctx* ctx, const rt_scene* device_scene,
                      const float ray_dir[4], const float* device_ray_origins,
                      int32_t width, int32_t height, int32_t row_begin,
@@ -289,6 +313,19 @@ int rt_scene_synthetic_device(rt_ctx* ctx, int32_t width, int32_t height,
 
 /* Texture conversion (MainState.cpp:1023-1037) on the host. */
 void rt_pack_rgba8(const int32_t* frame, int64_t n_pixels, uint32_t* out);
+
+/* Shade a hit buffer exactly as the trace would have (MainState.cpp:396-407,
+ * :952-955 / :1023-1037): out_format is RT_FORMAT_I32X4 (out = int32[4 *
+ * n_pixels]) or RT_FORMAT_RGBA8 (out = uint32[n_pixels]).  The same float
+ * sequence as the trace ((t / 180), 255 - n * 255, scalar * colour) and the
+ * reference's x86 (int): NaN and out-of-range values become INT32_MIN.  Only
+ * the colour arrays and counts of `scene` are read (host pointers), so a
+ * frame can be re-shaded with another colour table without tracing again.
+ * Returns RT_ERR_INVALID_ARG for an `object` outside
+ * [-1, num_cubes + num_spheres), or any other out_format; `out` may then be
+ * partly written. */
+int rt_shade_hits(const rt_hit* hits, int64_t n_pixels, const rt_scene* scene,
+                  int32_t out_format, void* out);
 
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`

@@ -78,7 +78,8 @@ int rt_debug_set_coarse_waves(rt_ctx* ctx, int waves);
  * ANDs its bin's mask words and classifies the candidates itself; scenes of
  * at most 1024 primitives): 0 (default) = automatic (frames above 4096 wave
  * tiles whose previous binned frame on this context had a box overdraw below
- * 4 frames for int32x4, 1 for RGBA8), 1 = wherever it applies, 2 = never. */
+ * 4 frames for int32x4, 1 for RGBA8 and HIT), 1 = wherever it applies,
+ * 2 = never. */
 int rt_debug_set_trace_bin(rt_ctx* ctx, int mode);
 
 /* How the overdraw verdict behind the automatic path choice reaches the
@@ -100,16 +101,17 @@ int rt_debug_last_overdraw(rt_ctx* ctx, double* frames);
 int rt_debug_set_coarse_cull(rt_ctx* ctx, int enable);
 /* Triangles join the coarse depth cull in bins whose wave tiles keep at
  * least this many candidates on average (0 = never, negative = the build's
- * defaults: 4 for int32x4 renders, 2 for RGBA8 renders; a value >= 0 applies
- * to both formats). */
+ * defaults: 4 for int32x4 renders, 2 for RGBA8 and HIT renders; a value >= 0
+ * applies to every format). */
 int rt_debug_set_coarse_cull_tri(rt_ctx* ctx, int min_candidates);
 /* ... and only in frames whose primitive boxes, summed, cover the frame at
  * least `frames` times (the trace is then bound by its tests rather than its
  * stores; 0 = every frame, negative = the build's defaults: 5 for int32x4
- * renders, 0 for RGBA8 renders, whose trace is bound by its tests, and in
- * either format only in bands of at least 768 coarse bins, since fewer coarse
- * waves cannot hide the cull's latency).  A value >= 0 applies to both
- * formats and every band size. */
+ * renders, 0 for RGBA8 renders, whose trace is bound by its tests, 2 for HIT
+ * renders, and in
+ * any format only in bands of at least 768 coarse bins, since fewer coarse
+ * waves cannot hide the cull's latency).  A value >= 0 applies to every
+ * format and every band size. */
 int rt_debug_set_coarse_cull_overdraw(rt_ctx* ctx, int frames);
 /* The bounds tri_t_bounds gives the trace's computed fp64 t over pixels
  * [xa, xb] x [ya, yb] (host evaluation; returns 0 without a bound). */

@@ -21,11 +21,12 @@ import numpy as np
 
 __all__ = [
     "RT_OK", "RT_ERR_INVALID_ARG", "RT_ERR_NO_DEVICE", "RT_ERR_HIP", "RT_ERR_OUT_OF_MEMORY",
-    "RT_ERR_UNSUPPORTED", "RT_FORMAT_I32X4", "RT_FORMAT_RGBA8", "RT_PATH_AUTO", "RT_PATH_BINNED",
+    "RT_ERR_UNSUPPORTED", "RT_FORMAT_I32X4", "RT_FORMAT_RGBA8", "RT_FORMAT_HIT", "RT_PATH_AUTO", "RT_PATH_BINNED",
     "RT_PATH_GENERIC", "RtError", "Scene", "Timing", "RayTracer", "MainState",
     "library", "library_path", "primary_ray_dir", "pack_rgba8", "cube_packed",
     "deg_to_rad", "encode_png", "EXPORTED_SYMBOLS", "CUBE_OP_DTYPE", "cube_ops", "render_multi",
-    "debug_glibc_sincosf", "host_register", "host_unregister",
+    "debug_glibc_sincosf", "host_register", "host_unregister", "HIT_DTYPE", "HIT_MISS_T",
+    "shade_hits",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -33,8 +34,13 @@ RT_OK = 0
 RT_ERR_INVALID_ARG, RT_ERR_NO_DEVICE, RT_ERR_HIP = -1, -2, -3
 RT_ERR_OUT_OF_MEMORY, RT_ERR_UNSUPPORTED = -4, -5
 RT_FORMAT_I32X4, RT_FORMAT_RGBA8 = 0, 1
+RT_FORMAT_HIT = 3  # (2 is reserved: RT_ERR_INVALID_ARG)
 RT_PATH_AUTO, RT_PATH_BINNED, RT_PATH_GENERIC = 0, 1, 2
-_FORMATS = {"i32x4": RT_FORMAT_I32X4, "rgba8": RT_FORMAT_RGBA8}
+_FORMATS = {"i32x4": RT_FORMAT_I32X4, "rgba8": RT_FORMAT_RGBA8, "hit": RT_FORMAT_HIT}
+# rt_hit (include/rt_hip.h): one pixel of a "hit" frame.  A miss is
+# (HIT_MISS_T, -1); object is the colour slot (cube c: c, sphere i: num_cubes + i).
+HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4")])
+HIT_MISS_T = np.float32(300000.0)
 _PATHS = {"auto": RT_PATH_AUTO, "binned": RT_PATH_BINNED, "generic": RT_PATH_GENERIC}
 
 # Every symbol include/rt_hip.h declares (tests check the .so exports them).
@@ -46,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "rt_pack_rgba8", "rt_abi_version", "rt_cube_build_device", "rt_scene_synthetic_device",
     "rt_render_multi", "rt_shared_alloc", "rt_shared_open", "rt_shared_close", "rt_shared_free",
     "rt_host_register", "rt_host_unregister", "rt_reserve", "rt_last_kernel", "rt_fnv1a64",
+    "rt_shade_hits",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -150,6 +157,7 @@ def library() -> ctypes.CDLL:
         "rt_pack_rgba8": (None, [vp, ctypes.c_int64, vp]),
         "rt_abi_version": (ctypes.c_int, []),
         "rt_fnv1a64": (ctypes.c_uint64, [vp, ctypes.c_int64, ctypes.c_uint64]),
+        "rt_shade_hits": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), i32, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -262,6 +270,13 @@ def pack_rgba8(frame: np.ndarray) -> np.ndarray:
     return out
 
 
+def _frame_layout(fmt: str, rows: int, width: int):
+    """(shape, dtype) of a host frame of `rows` x `width` pixels in `fmt`."""
+    if fmt == "i32x4":
+        return (rows, width, 4), np.dtype(np.int32)
+    return (rows, width), HIT_DTYPE if fmt == "hit" else np.dtype(np.uint32)
+
+
 FNV1A64_BASIS = 0xcbf29ce484222325
 
 
@@ -272,6 +287,8 @@ def fnv1a64(words, basis: int = FNV1A64_BASIS) -> int:
     if not isinstance(words, np.ndarray):
         words = words.contiguous().numpy()
     words = np.ascontiguousarray(words)
+    if words.dtype == HIT_DTYPE:  # a hit frame: its two words per pixel
+        words = words.view(np.uint32)
     if words.dtype.itemsize != 4:
         raise ValueError(f"fnv1a64 hashes 32-bit words, got {words.dtype}")
     return int(library().rt_fnv1a64(_ptr(words), words.size, basis))
@@ -369,8 +386,7 @@ def render_multi(tracers, scene: Scene, width: int, height: int,
     org = None if ray_origins is None else np.ascontiguousarray(ray_origins, np.float32)
     if org is not None and org.size != 4 * width * height:
         raise ValueError("ray_origins must hold width*height float4")
-    shape = (re - rb, width, 4) if fmt == "i32x4" else (re - rb, width)
-    out = np.empty(shape, np.int32 if fmt == "i32x4" else np.uint32)
+    out = np.empty(*_frame_layout(fmt, re - rb, width))
     ctxs = (ctypes.c_void_p * len(tracers))(*[t.handle.value for t in tracers])
     times = (_Timing * len(tracers))()
     sc = scene.as_c()
@@ -380,6 +396,25 @@ def render_multi(tracers, scene: Scene, width: int, height: int,
     names = {RT_PATH_BINNED: "binned", RT_PATH_GENERIC: "generic"}
     return out, [Timing(t.total_us, t.upload_us, t.kernel_us, t.download_us,
                         names.get(t.path, "idle")) for t in times]
+
+
+def shade_hits(hits: np.ndarray, scene: Scene, fmt: str = "i32x4") -> np.ndarray:
+    """rt_shade_hits: the frame the trace would have returned for a "hit"
+    frame (HIT_DTYPE, any shape), shaded with `scene`'s colour table on the
+    host: int32 (..., 4) for "i32x4", uint32 (...) for "rgba8".  Only the
+    scene's colours and counts are read, so another colour table re-shades a
+    frame without tracing again."""
+    if fmt not in ("i32x4", "rgba8"):
+        raise ValueError("shade_hits gives an i32x4 or an rgba8 frame")
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype != HIT_DTYPE:
+        raise ValueError(f"hits must be a HIT_DTYPE array, got {hits.dtype}")
+    out = (np.empty(hits.shape + (4,), np.int32) if fmt == "i32x4"
+           else np.empty(hits.shape, np.uint32))
+    sc = scene.as_c()
+    _check(library().rt_shade_hits(_ptr(hits), hits.size, ctypes.byref(sc), _FORMATS[fmt],
+                                   _ptr(out)), "rt_shade_hits")
+    return out
 
 
 def host_register(buf: np.ndarray) -> None:
@@ -427,7 +462,8 @@ class RayTracer:
                fmt: str = "i32x4", path: str = "auto",
                out: Optional[np.ndarray] = None) -> Tuple[np.ndarray, Timing]:
         """Synchronous host-buffer render (rt_render_path).  Returns the frame
-        (rows x width x 4 int32, or rows x width uint32 for rgba8), written
+        (rows x width x 4 int32, rows x width uint32 for rgba8, or rows x
+        width HIT_DTYPE records for hit), written
         into `out` when given (a reused buffer, like the reference's
         `pixels` vector, MainState.cpp:215, avoids first-touch page faults
         in the readback)."""
@@ -436,12 +472,11 @@ class RayTracer:
         org = None if ray_origins is None else np.ascontiguousarray(ray_origins, np.float32)
         if org is not None and org.size != 4 * width * height:
             raise ValueError("ray_origins must hold width*height float4")
-        shape = (re - rb, width, 4) if fmt == "i32x4" else (re - rb, width)
-        dtype = np.int32 if fmt == "i32x4" else np.uint32
+        shape, dtype = _frame_layout(fmt, re - rb, width)
         if out is None:
             out = np.empty(shape, dtype)
         elif out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
-            raise ValueError(f"out must be a C-contiguous {dtype.__name__} array of {shape}")
+            raise ValueError(f"out must be a C-contiguous {dtype.name} array of {shape}")
         t = _Timing()
         sc = scene.as_c()
         _check(library().rt_render_path(self._ctx, ctypes.byref(sc), _ptr(d), _ptr(org), width,

@@ -21,7 +21,7 @@ int check_args(const rt_scene* s, int32_t width, int32_t height, int32_t row_beg
         return RT_ERR_INVALID_ARG;
     if (s->num_cubes > 0 && (!s->cube_vertices || !s->cube_colours)) return RT_ERR_INVALID_ARG;
     if ((int64_t)12 * s->num_cubes + s->num_spheres > (int64_t)1 << 30) return RT_ERR_INVALID_ARG;
-    if (fmt != RT_FORMAT_I32X4 && fmt != RT_FORMAT_RGBA8) return RT_ERR_INVALID_ARG;
+    if (!format_ok(fmt)) return RT_ERR_INVALID_ARG;
     return RT_OK;
 }
 
@@ -29,13 +29,13 @@ int check_reserve(int32_t width, int32_t rows, int32_t num_spheres, int32_t num_
                   int32_t fmt) {
     if (width <= 0 || rows <= 0 || width > (1 << 24) || rows > (1 << 24) || num_spheres < 0 ||
         num_cubes < 0 || (int64_t)12 * num_cubes + num_spheres > (int64_t)1 << 30 ||
-        (fmt != RT_FORMAT_I32X4 && fmt != RT_FORMAT_RGBA8))
+        !format_ok(fmt))
         return RT_ERR_INVALID_ARG;
     return RT_OK;
 }
 
 size_t frame_bytes(int32_t width, int32_t rows, int32_t fmt) {
-    return (size_t)width * (size_t)rows * (fmt == RT_FORMAT_I32X4 ? 16u : 4u);
+    return (size_t)width * (size_t)rows * pixel_bytes(fmt);
 }
 
 SceneLayout scene_layout(int32_t num_spheres, int32_t num_cubes) {

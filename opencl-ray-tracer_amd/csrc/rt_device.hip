@@ -86,6 +86,17 @@
                                          // frame (its trace is bound by its tests, not by
                                          // its stores)
 #endif
+// ... and for hit-buffer (RT_FORMAT_HIT) renders, measured on HIT frames of
+// config 3's scene at five object sizes: the triangle
+// threshold of 2 is 1.6-2 us per frame faster than 4 wherever the cull runs,
+// and the cull pays from a box overdraw of about 2 frames on (1.4: 41.5 us
+// without, 44.2 with; 2.8: 43.7 / 43.1; 4.3: 49.6 / 43.5)
+#ifndef RT_COARSE_CULL_TRI_HIT
+#define RT_COARSE_CULL_TRI_HIT 2
+#endif
+#ifndef RT_COARSE_CULL_OVERDRAW_HIT
+#define RT_COARSE_CULL_OVERDRAW_HIT 2
+#endif
 #ifndef RT_SPLIT4_TILES
 #define RT_SPLIT4_TILES 2048  // trace3_split_kernel with 4 waves per tile up to this many tiles
 #endif
@@ -201,10 +212,12 @@ struct rt_ctx {
     // many candidates on average (0 = never)
     int coarse_cull_tri = RT_COARSE_CULL_TRI;
     int coarse_cull_tri_rgba8 = RT_COARSE_CULL_TRI_RGBA8;  // (RGBA8 renders)
+    int coarse_cull_tri_hit = RT_COARSE_CULL_TRI_HIT;      // (HIT renders)
     // ... in frames whose boxes' summed area is at least this many frames
     // (int32x4 renders; RGBA8 renders take the second gate)
     unsigned coarse_cull_overdraw = RT_COARSE_CULL_OVERDRAW;
     unsigned coarse_cull_overdraw_rgba8 = RT_COARSE_CULL_OVERDRAW_RGBA8;
+    unsigned coarse_cull_overdraw_hit = RT_COARSE_CULL_OVERDRAW_HIT;
     // ... in bands of at least this many coarse bins
     int64_t coarse_cull_tri_bins = RT_COARSE_CULL_TRI_BINS;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -324,12 +337,13 @@ int enqueue_verdict_copy(rt_ctx* ctx, hipStream_t stream) {
 #ifndef RT_TILE_WIDE
 #define RT_TILE_WIDE 128
 #endif
-// nontemporal frame stores per build: bit 0 int32x4, bit 1 RGBA8
+// nontemporal frame stores per build: bit 0 int32x4, bit 1 RGBA8, bit 2 HIT
 #ifndef RT_NT_NARROW
-#define RT_NT_NARROW 2  // the 16x16 build: RGBA8 only (int32x4 measured much slower)
+#define RT_NT_NARROW 6  // the 16x16 build: RGBA8 and HIT (int32x4 measured much slower; HIT
+                        // frames 1-2 % faster with them on one stream, 4-6 % at two in flight)
 #endif
 #ifndef RT_NT_WIDE
-#define RT_NT_WIDE 3
+#define RT_NT_WIDE 7
 #endif
 #ifndef RT_ROWS_NARROW
 #define RT_ROWS_NARROW 4  // pixels per lane in the 16x16 build (A/B variants: 8 = 16x32 tiles)
@@ -387,7 +401,7 @@ constexpr int64_t kWideTileBytes = (int64_t)1 << 29;
 
 // rt_debug_set_tile_variant: 0 = by frame size, 1 = 16x16, 2 = wide (128x2)
 bool use_wide_tiles(const rt_ctx* ctx, int32_t width, int32_t rows, int32_t fmt) {
-    const int64_t bytes = (int64_t)width * rows * (fmt == RT_FORMAT_I32X4 ? 16 : 4);
+    const int64_t bytes = (int64_t)width * rows * (int64_t)rt_args::pixel_bytes(fmt);
     return ctx->tile_variant == 2 || (ctx->tile_variant == 0 && bytes >= kWideTileBytes);
 }
 
@@ -737,7 +751,7 @@ int rt_render_multi(rt_ctx* const* ctxs, int32_t num_ctx, const rt_scene* scene,
     // contexts than rows leave the surplus ones idle
     const int32_t rows = row_end - row_begin;
     const int32_t n = std::min(num_ctx, rows);
-    const size_t row_bytes = (size_t)width * (out_format == RT_FORMAT_I32X4 ? 16 : 4);
+    const size_t row_bytes = (size_t)width * rt_args::pixel_bytes(out_format);
     std::vector<int> status((size_t)n, RT_OK);
     auto band = [&](int32_t i) {
         const int32_t rb = row_begin + (int32_t)((int64_t)rows * i / n);
@@ -969,6 +983,7 @@ int rt_debug_set_coarse_cull_tri(rt_ctx* ctx, int min_candidates) {
     if (!ctx) return RT_ERR_INVALID_ARG;
     ctx->coarse_cull_tri = min_candidates < 0 ? RT_COARSE_CULL_TRI : min_candidates;
     ctx->coarse_cull_tri_rgba8 = min_candidates < 0 ? RT_COARSE_CULL_TRI_RGBA8 : min_candidates;
+    ctx->coarse_cull_tri_hit = min_candidates < 0 ? RT_COARSE_CULL_TRI_HIT : min_candidates;
     return RT_OK;
 }
 
@@ -977,6 +992,7 @@ int rt_debug_set_coarse_cull_overdraw(rt_ctx* ctx, int frames) {
     ctx->coarse_cull_overdraw = frames < 0 ? RT_COARSE_CULL_OVERDRAW : (unsigned)frames;
     ctx->coarse_cull_overdraw_rgba8 =
         frames < 0 ? RT_COARSE_CULL_OVERDRAW_RGBA8 : (unsigned)frames;
+    ctx->coarse_cull_overdraw_hit = frames < 0 ? RT_COARSE_CULL_OVERDRAW_HIT : (unsigned)frames;
     // an explicit gate applies to every band size (the tests force the cull
     // on small frames this way)
     ctx->coarse_cull_tri_bins = frames < 0 ? RT_COARSE_CULL_TRI_BINS : 0;

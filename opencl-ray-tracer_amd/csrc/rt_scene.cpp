@@ -360,6 +360,48 @@ void rt_pack_rgba8(const int32_t* frame, int64_t n_pixels, uint32_t* out) {
     }
 }
 
+// (int)f as x86-64 cvttss2si: truncation, NaN / out of range -> INT32_MIN
+// (a C++ (int) of such a float is undefined).
+static int32_t cvt_i32(float f) {
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? static_cast<int32_t>(f) : INT32_MIN;
+}
+
+int rt_shade_hits(const rt_hit* hits, int64_t n_pixels, const rt_scene* scene,
+                  int32_t out_format, void* out) {
+    if (!hits || !scene || !out || n_pixels < 0 || scene->num_cubes < 0 ||
+        scene->num_spheres < 0 || (scene->num_cubes > 0 && !scene->cube_colours) ||
+        (scene->num_spheres > 0 && !scene->sphere_colours) ||
+        (out_format != RT_FORMAT_I32X4 && out_format != RT_FORMAT_RGBA8))
+        return RT_ERR_INVALID_ARG;
+    const int64_t n_slots = static_cast<int64_t>(scene->num_cubes) + scene->num_spheres;
+    int32_t* out_i = static_cast<int32_t*>(out);
+    uint32_t* out_w = static_cast<uint32_t*>(out);
+    for (int64_t i = 0; i < n_pixels; ++i) {
+        const float closest = hits[i].t;
+        const int64_t slot = hits[i].object;
+        if (slot < -1 || slot >= n_slots) return RT_ERR_INVALID_ARG;
+        // closestColour starts as (0, 0, 0, 255) (MainState.cpp:344)
+        static const float kNone[4] = {0.0f, 0.0f, 0.0f, 255.0f};
+        const float* c = slot < 0                   ? kNone
+                         : slot < scene->num_cubes ? scene->cube_colours + 4 * slot
+                                                   : scene->sphere_colours +
+                                                         4 * (slot - scene->num_cubes);
+        int32_t p[4] = {0, 0, 0, 255};
+        if (!(closest == 300000.0f)) {  // MainState.cpp:397-407
+            const float normalised = (closest - 0.0f) / (180.0f - 0.0f);
+            const float scalar = 255.0f - (normalised * 255.0f);
+            p[0] = cvt_i32(scalar * c[0]);
+            p[1] = cvt_i32(scalar * c[1]);
+            p[2] = cvt_i32(scalar * c[2]);
+        }
+        if (out_format == RT_FORMAT_I32X4)
+            std::memcpy(out_i + 4 * i, p, sizeof p);
+        else
+            rt_pack_rgba8(p, 1, out_w + i);
+    }
+    return RT_OK;
+}
+
 uint64_t rt_fnv1a64(const void* words, int64_t n_words, uint64_t basis) {
     const uint32_t* w = static_cast<const uint32_t*>(words);
     uint64_t h = basis;

@@ -7,11 +7,14 @@
 // Kernels (DESIGN.md §3), per frame, by scene size:
 //   <= 128 primitives, grid resident at once: frame_small_kernel (one launch)
 //   <= 512 primitives: prep_kernel -> trace_small_kernel
-//   <= 1024 primitives, box overdraw below 4 frames (int32x4) / 1 (RGBA8),
+//   <= 1024 primitives, box overdraw below 4 frames (int32x4) / 1 (RGBA8, HIT),
 //   frames above 4096 wave tiles: prep_kernel -> trace_bin_kernel
 //   otherwise:         prep_kernel -> coarse3_kernel -> trace3_kernel
 //                      (trace3_split_kernel on small frames)
 //   explicit origins / other directions: generic_kernel (brute force)
+// Every pixel-writing kernel exists per output format (kFmt): int32x4, the
+// Texture's RGBA8 word, or RT_FORMAT_HIT (rt_hit: the walk's closest and
+// colour slot, unshaded).
 namespace {
 
 // Build-time geometry / feature knobs (A/B variants: scripts/variants.sh).
@@ -471,10 +474,23 @@ struct SceneDev {
     int n_spheres, n_cubes;
 };
 
-__device__ inline int4v collide_generic(const SceneDev& s, float4 origin, float4 dir) {
+// The collide loop (MainState.cpp:345-394) up to, not including, the shade:
+// `closest` and what the winner leaves behind.  kSlot: its colour slot (cube
+// c: c, sphere i: n_cubes + i; -1 beside kFar: no hit), for RT_FORMAT_HIT.
+// Otherwise its colour, loaded when it wins as the reference does (the two
+// colour formats' code is what it was before the slot existed; `slot` is
+// then not tracked and stays -1).
+struct GenericHit {
+    float closest;
+    int slot;
+    float4 colour;
+};
+template <bool kSlot>
+__device__ inline GenericHit closest_generic(const SceneDev& s, float4 origin, float4 dir) {
     const double o[3] = {origin.x, origin.y, origin.z};
     const double d[3] = {dir.x, dir.y, dir.z};
     float closest = kFar;
+    int slot = -1;
     float4 colour = make_float4(0.0f, 0.0f, 0.0f, 255.0f);
     for (int c = 0; c < s.n_cubes; ++c) {
         const float4* tri = s.cube_vertices + 36 * c;
@@ -484,7 +500,10 @@ __device__ inline int4v collide_generic(const SceneDev& s, float4 origin, float4
             double t;
             if (intersect_tri(o, d, v0, v1, v2, &t) == 1 && (float)t < closest) {
                 closest = (float)t;
-                colour = s.cube_colours[c];
+                if constexpr (kSlot)
+                    slot = c;
+                else
+                    colour = s.cube_colours[c];
             }
         }
     }
@@ -493,10 +512,36 @@ __device__ inline int4v collide_generic(const SceneDev& s, float4 origin, float4
         if (dist == 0.0f) continue;
         if (dist < closest) {
             closest = dist;
-            colour = s.sphere_colours[i];
+            if constexpr (kSlot)
+                slot = s.n_cubes + i;
+            else
+                colour = s.sphere_colours[i];
         }
     }
-    return shade(closest, colour);
+    return GenericHit{closest, slot, colour};
+}
+
+// A lane's RT_FORMAT_HIT pixel in the kernels' pixel registers: the rt_hit
+// words in x and y (z, w unused).
+__device__ __forceinline__ int4v hit_pixel(float closest, int slot) {
+    return int4v{(int)__float_as_uint(closest), slot, 0, 0};
+}
+
+// One hit_pixel to pixel `idx` of an rt_hit frame.
+__device__ __forceinline__ void store_hit(void* __restrict__ out, int64_t idx, int4v pix) {
+    reinterpret_cast<int2*>(out)[idx] = make_int2(pix.x, pix.y);
+}
+
+// The reference's pixel: the collide loop, then its shade (int32x4; the
+// Texture word is packed from it) -- or, for RT_FORMAT_HIT, the loop's result
+// itself (hit_pixel).
+template <int kFmt = RT_FORMAT_I32X4>
+__device__ inline int4v collide_generic(const SceneDev& s, float4 origin, float4 dir) {
+    const GenericHit h = closest_generic<kFmt == RT_FORMAT_HIT>(s, origin, dir);
+    if constexpr (kFmt == RT_FORMAT_HIT)
+        return hit_pixel(h.closest, h.slot);
+    else
+        return shade(h.closest, h.colour);
 }
 
 __global__ void __launch_bounds__(kThreads) generic_kernel(
@@ -510,6 +555,10 @@ __global__ void __launch_bounds__(kThreads) generic_kernel(
         const int y = row_begin + (int)(i / width);
         // `origins` starts at row row_begin (the band's rows only)
         const float4 o = origins ? origins[i] : make_float4((float)x, (float)y, 0.0f, 1.0f);
+        if (out_format == RT_FORMAT_HIT) {  // (kernel-uniform)
+            store_hit(out, i, collide_generic<RT_FORMAT_HIT>(scene, o, dir));
+            continue;
+        }
         const int4v p = collide_generic(scene, o, dir);
         if (out_format == RT_FORMAT_I32X4)
             reinterpret_cast<int4v*>(out)[i] = p;
@@ -960,11 +1009,14 @@ __device__ __forceinline__ void classify(const Cls& k, bool is_tri, float x0, fl
     }
 }
 
-// Pixel value of the Texture format (MainState.cpp:1026-1036) or int32x4.
+// Pixel value of the Texture format (MainState.cpp:1026-1036), int32x4, or
+// the rt_hit words of hit_pixel.
 template <int kFmt>
 __device__ __forceinline__ void store_fmt(void* __restrict__ out, int64_t idx, int4v pix) {
     if (kFmt == RT_FORMAT_I32X4)
         reinterpret_cast<int4v*>(out)[idx] = pix;
+    else if (kFmt == RT_FORMAT_HIT)
+        store_hit(out, idx, pix);
     else
         reinterpret_cast<unsigned*>(out)[idx] = pack_rgba8(pix);
 }
@@ -979,6 +1031,9 @@ __device__ __forceinline__ void store_fmt(void* __restrict__ out, int64_t idx, i
 // DESIGN.md §3.5).
 constexpr bool kNtI32 = (RT_NT_STORES & 1) != 0;
 constexpr bool kNtRgba8 = (RT_NT_STORES & 2) != 0;
+// RT_FORMAT_HIT frames (8-byte pixels): bit 2 (DESIGN.md §3.5)
+constexpr bool kNtHit = (RT_NT_STORES & 4) != 0;
+typedef unsigned uint2v __attribute__((ext_vector_type(2)));
 // (raw buffer stores: the tile origin in a buffer descriptor, the lane's
 // 32-bit byte offset in a VGPR, the row's byte step as the scalar offset;
 // aux bit 1 is nt on gfx950, the same bit __builtin_nontemporal_store sets)
@@ -987,6 +1042,9 @@ __device__ __forceinline__ void store_shaded(__amdgpu_buffer_rsrc_t tile, unsign
                                              int row_off, int4v pix) {
     if (kFmt == RT_FORMAT_I32X4)
         __builtin_amdgcn_raw_buffer_store_b128(pix, tile, (int)lane_off, row_off, kNtI32 ? 2 : 0);
+    else if (kFmt == RT_FORMAT_HIT)
+        __builtin_amdgcn_raw_buffer_store_b64(uint2v{(unsigned)pix.x, (unsigned)pix.y}, tile,
+                                              (int)lane_off, row_off, kNtHit ? 2 : 0);
     else
         __builtin_amdgcn_raw_buffer_store_b32(pix.x, tile, (int)lane_off, row_off,
                                               kNtRgba8 ? 2 : 0);
@@ -1002,9 +1060,18 @@ __device__ __forceinline__ unsigned pack_bytes(int r, int g, int b) {
 
 // Shade (MainState.cpp:396-407) one lane's kRowsPerLane pixels.  Int32x4:
 // pix[j] is the pixel.  RGBA8: pix[j].x is the packed Texture word.
+// RT_FORMAT_HIT: no shade at all, pix[j] is hit_pixel: the walk's closest[j]
+// and hit[j] as they stand (every walk starts them at kFar / -1 and
+// take_rows only ever writes a slot >= 0 beside a t < closest, so a miss is
+// {kFar, -1} and nothing else).
 template <int kMode = 0, int kFmt = RT_FORMAT_I32X4>
 __device__ __forceinline__ void shade_pixels(const float4* __restrict__ colours,
                                              const float* closest, const int* hit, int4v* pix) {
+    if (kFmt == RT_FORMAT_HIT) {
+#pragma unroll
+        for (int j = 0; j < kRowsPerLane; ++j) pix[j] = hit_pixel(closest[j], hit[j]);
+        return;
+    }
     bool lane_hit = false;
 #pragma unroll
     for (int j = 0; j < kRowsPerLane; ++j) lane_hit |= hit[j] >= 0;
@@ -1101,8 +1168,8 @@ __device__ __forceinline__ void shade_pixels(const float4* __restrict__ colours,
 
 // Store one lane's kRowsPerLane shaded pixels (pix_dx / pix_dy apart) of the
 // wave tile at (rel_x, rel_y) of the band (rows from the band's first), in
-// the Texture format (MainState.cpp:1026-1036, packed by shade_pixels) or
-// int32x4.  Each row's address is a wave-uniform base (SGPRs: the tile
+// the Texture format (MainState.cpp:1026-1036, packed by shade_pixels),
+// int32x4 or rt_hit.  Each row's address is a wave-uniform base (SGPRs: the tile
 // origin plus the row's step) and the lane's 32-bit byte offset, so the
 // stores take the saddr + voffset form with no per-pixel 64-bit address
 // arithmetic (round 4).  `full`: the whole tile lies inside the frame band,
@@ -1111,7 +1178,7 @@ template <int kMode, int kFmt>
 __device__ __forceinline__ void store_rows(const int4v* pix, int rel_x, int rel_y, int lane,
                                            int width, int band_h, bool full,
                                            void* __restrict__ out) {
-    constexpr int kBytes = kFmt == RT_FORMAT_I32X4 ? 16 : 4;
+    constexpr int kBytes = (int)rt_args::pixel_bytes(kFmt);
     const int lx = lane % kLanesX, ly = lane / kLanesX;
     // ly * width as a 24-bit multiply (width <= 2^24, so width - 1 fits)
     const unsigned lane_off =
@@ -1722,249 +1789,29 @@ __device__ __forceinline__ unsigned wave_max_key(const float* closest) {
 static_assert((kTiles & (kTiles - 1)) == 0, "tiles per bin: a power of two");
 // (Arguments in the order the wave needs them: with kernel-argument
 // preloading the first 14 dwords arrive in SGPRs.)
+// (The body is rt_trace3_body.inc, included into the kernel's two entry
+// points: the same text, so the same code, under two names.)
 template <int kMode, int kFmt>
 __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_kernel(
     const int* __restrict__ counts, const int* __restrict__ lists,
     const TriRec* __restrict__ tri, const SphRec* __restrict__ sph, int n_cx, int half_cap,
     int width, int row_begin, int row_end, int n_cubes, const float4* __restrict__ colours,
     void* __restrict__ out, SceneDev scene, float4 dir, int n_tiles_x, int out_format) {
-    // (unsigned: the divisions by powers of two are shifts and masks)
-    const unsigned bid = blockIdx.x;
-    const int cbx = (int)(bid / kTiles), cby = (int)blockIdx.y;
-    const int cb = cby * n_cx + cbx;
-    const unsigned t = bid % kTiles;  // the tile of the bin (wave-uniform)
-#if RT_TIMELINE
-    const int tile = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
-#endif
-    const int lane = threadIdx.x & 63;
-    const int n_tri = 12 * n_cubes;
-    (void)n_tiles_x;
-    (void)out_format;
-    TL_MARK(tl0);
-#if RT_TIMELINE
-    const unsigned long long tlc0 = __builtin_amdgcn_s_memtime();
-    unsigned tl1 = 0, tl2 = 0;
-#endif
-    const int rel_x = cbx * kCoarseW + (int)(t % kTilesX) * kWaveTile;
-    const int rel_y = cby * kCoarseH + (int)(t / kTilesX) * kWaveTileH;  // vs row_begin
-    const int tile_x = rel_x, tile_y = row_begin + rel_y;
-    const int x = tile_x + (lane % kLanesX);  // the lane's pixel 0
-    const int y0 = tile_y + (lane / kLanesX);
-    // wave-uniform: tiles past the frame's right or bottom edge render nothing
-    const bool tile_in = rel_x < width && rel_y < row_end - row_begin;
+#include "rt_trace3_body.inc"
+}
 
-    // the bin's count (-1: non-finite scene data, see coarse3_kernel) is the
-    // wave's first data load
-#if RT_WALK_BALLOT == 2
-    // issued beside the count's load, not after it: the list's first 64
-    // entries (entry e on lane e; a bin's list holds half_cap entries)
-    int spec_id = 0, spec_tm = 0;
-    {
-        const int* __restrict__ ids0 = lists + (int64_t)cb * kListStride * half_cap;
-        const int* __restrict__ tms0 = ids0 + (1 + (int)(t / kTilesPerWord)) * half_cap;
-        if (lane < half_cap) {
-            spec_id = ids0[lane];
-            spec_tm = tms0[lane];
-        }
-    }
-#endif
-    const int count_raw = kMode == 1 ? 0 : counts[cb];
-    if (tile_in && kMode == 0 && count_raw < 0) {
-        // Non-finite scene data: run the reference algorithm verbatim.
-#pragma unroll 1
-        for (int j = 0; j < kRowsPerLane; ++j) {
-            const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
-            if (xj < width && y < row_end)
-                store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
-                                                dir));
-        }
-    } else if (tile_in) {
-    int4v pix[kRowsPerLane];  // assigned after the walk (not live during it)
-    float closest[kRowsPerLane];
-    int hit[kRowsPerLane];
-    double px[kRowsPerLane], py[kRowsPerLane];
-    float pxf[kRowsPerLane], pyf[kRowsPerLane];
-#pragma unroll
-    for (int j = 0; j < kRowsPerLane; ++j) {
-        closest[j] = kFar;
-        hit[j] = -1;
-        py[j] = (double)(y0 + pix_dy(j));
-        pyf[j] = (float)(y0 + pix_dy(j));
-        px[j] = (double)(x + pix_dx(j));
-        pxf[j] = (float)(x + pix_dx(j));
-    }
-#if RT_DEPTH_CULL
-    // order_key of the largest `closest` in the tile, refreshed lazily
-    unsigned tile_max_key = order_key(kFar);
-    bool dirty = false;
-#endif
-    const int count = count_raw < 0 ? 0 : count_raw;
-    const int* __restrict__ ids = lists + (int64_t)cb * kListStride * half_cap;
-    const int* __restrict__ tms = ids + (1 + (int)(t / kTilesPerWord)) * half_cap;  // its word
-    const int tm_shift = kTileBits * (int)(t % kTilesPerWord);
-#if RT_TIMELINE
-    tl1 = rt_now();
-#endif
-#if RT_WALK_BALLOT
-    // The bin's list 64 entries at a time as vector loads (entry e on lane
-    // e), this tile's keep bits in one ballot, and only the kept entries
-    // visited (s_ff1 over the mask, id and bits by v_readlane): the walk no
-    // longer spends scalar instructions on the bin's entries this tile does
-    // not keep (most of them), in primitive order as before.
-    for (int c0 = 0; c0 < count; c0 += 64) {
-        const int e = c0 + lane;
-        int idl = 0;
-        unsigned bl = 0u;
-        if (e < count) {
-#if RT_WALK_BALLOT == 2
-            idl = c0 == 0 ? spec_id : ids[e];
-            bl = ((unsigned)(c0 == 0 ? spec_tm : tms[e]) >> tm_shift) & kTileMask;
-#else
-            idl = ids[e];
-            bl = ((unsigned)tms[e] >> tm_shift) & kTileMask;
-#endif
-        }
-        unsigned long long keep = __ballot((bl & kKeepMask) != 0u);
-        while (keep) {
-            const int k = __builtin_ctzll(keep);
-            keep &= keep - 1ull;
-            const int p = __builtin_amdgcn_readlane(idl, k);
-            const unsigned bits = (unsigned)__builtin_amdgcn_readlane((int)bl, k);
-            if (kMode == 2) {
-                hit[0] = hit[0] > p ? hit[0] : -1;
-                continue;
-            }
-            // both branches produce t per row (NaN: may not take); closest
-            // and hit are updated once, after them (round 4: trace 1-3 %
-            // faster than a test-and-update in each branch, DESIGN.md §3.5)
-            float tc[kRowsPerLane];
-            int slot;
-            if (p < n_tri) {
-                const TriRec r = tri_at(tri, p);
-                asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-                if constexpr (kRecomputeXY)
-                    tri_rows_fresh(r, bits, px[0], py[0], tc);
-                else
-                    tri_rows(r, bits, px, py, tc);
-                slot = p / 12;
-            } else {
-                const SphRec r = sph_at(sph, p - n_tri);
-#if RT_DEPTH_CULL
-                // t0 >= tmin >= every closest: no lane can take it (strict <)
-                if (dirty) {
-                    tile_max_key = wave_max_key(closest);
-                    dirty = false;
-                }
-                if (r.tmin_key >= tile_max_key) continue;
-#endif
-                if constexpr (kRecomputeXY)
-                    sph_rows_fresh(r, bits, pxf[0], pyf[0], tc);
-                else
-                    sph_rows(r, bits, pxf, pyf, tc);
-                slot = n_cubes + (p - n_tri);
-            }
-            take_rows(tc, slot, closest, hit);
-#if RT_DEPTH_CULL
-            dirty = true;
-#endif
-        }
-    }
-#else
-    for (int i0 = 0; i0 < count; i0 += 8) {
-        int idv[8], tmv[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            idv[k] = ids[i0 + k];  // half_cap is a multiple of 8 past the count
-            tmv[k] = tms[i0 + k];
-        }
-        const int n = min(8, count - i0);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (k >= n) break;
-            const unsigned bits = ((unsigned)tmv[k] >> tm_shift) & kTileMask;
-            if (!(bits & kKeepMask)) continue;
-            const int p = idv[k];
-            if (kMode == 2) {
-                hit[0] = hit[0] > p ? hit[0] : -1;
-                continue;
-            }
-            // both branches produce t per row (NaN: may not take); closest
-            // and hit are updated once, after them (round 4: trace 1-3 %
-            // faster than a test-and-update in each branch, DESIGN.md §3.5)
-            float tc[kRowsPerLane];
-            int slot;
-            if (p < n_tri) {
-                const TriRec r = tri_at(tri, p);
-                asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-                if constexpr (kRecomputeXY)
-                    tri_rows_fresh(r, bits, px[0], py[0], tc);
-                else
-                    tri_rows(r, bits, px, py, tc);
-                slot = p / 12;
-            } else {
-                const SphRec r = sph_at(sph, p - n_tri);
-#if RT_DEPTH_CULL
-                // t0 >= tmin >= every closest: no lane can take it (strict <)
-                if (dirty) {
-                    tile_max_key = wave_max_key(closest);
-                    dirty = false;
-                }
-                if (r.tmin_key >= tile_max_key) continue;
-#endif
-                if constexpr (kRecomputeXY)
-                    sph_rows_fresh(r, bits, pxf[0], pyf[0], tc);
-                else
-                    sph_rows(r, bits, pxf, pyf, tc);
-                slot = n_cubes + (p - n_tri);
-            }
-            take_rows(tc, slot, closest, hit);
-#if RT_DEPTH_CULL
-            dirty = true;
-#endif
-        }
-    }
-#endif
-#if RT_TIMELINE
-    tl2 = rt_now();
-#endif
-#if RT_EXTRA_VALU || RT_EXTRA_SALU
-    {
-        // diagnostics only (scripts/variants.sh): RT_EXTRA_VALU extra VALU /
-        // RT_EXTRA_SALU extra SALU instructions per wave, to price issue in
-        // this kernel (DESIGN.md §3.3)
-        float xa = closest[0], xb = closest[1];
-#pragma unroll
-        for (int q = 0; q < RT_EXTRA_VALU / 2; ++q) {
-            asm volatile("v_add_f32 %0, %0, %1" : "+v"(xa) : "v"(xb));
-            asm volatile("v_add_f32 %0, %0, %1" : "+v"(xb) : "v"(xa));
-        }
-        unsigned sa = (unsigned)count, sb = (unsigned)cb;
-#pragma unroll
-        for (int q = 0; q < RT_EXTRA_SALU / 2; ++q) {
-            asm volatile("s_add_u32 %0, %0, %1" : "+s"(sa) : "s"(sb));
-            asm volatile("s_add_u32 %0, %0, %1" : "+s"(sb) : "s"(sa));
-        }
-        if (xa == 1234.5f && xb == 1234.5f && sa == 7u) hit[0] = -2;  // never (keeps the chains)
-    }
-#endif
-    shade_pixels<kMode, kFmt>(colours, closest, hit, pix);
-    const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
-    store_rows<kMode, kFmt>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
-    }  // finite scene, tile inside the frame
-#if RT_TIMELINE
-    {
-        const unsigned tl3 = rt_now();
-        const unsigned long long tlc3 = __builtin_amdgcn_s_memtime();
-        if (lane == 0) {
-            unsigned* o = g_timeline + 8 * (int64_t)tile;
-            o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = tl3;
-            o[4] = (unsigned)tlc0; o[5] = (unsigned)tlc3;
-            o[6] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-            o[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        }
-    }
-#endif
+// The RT_FORMAT_HIT instance under a name of its own: the library's
+// trace3_kernel<mode, format> symbols stay the two colour formats' (the
+// shipped build has exactly <0, int32x4> and <0, RGBA8>; tests/test_capi.py
+// counts them to prove that no ablation mode is compiled in).
+template <int kMode>
+__global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_hit_kernel(
+    const int* __restrict__ counts, const int* __restrict__ lists,
+    const TriRec* __restrict__ tri, const SphRec* __restrict__ sph, int n_cx, int half_cap,
+    int width, int row_begin, int row_end, int n_cubes, const float4* __restrict__ colours,
+    void* __restrict__ out, SceneDev scene, float4 dir, int n_tiles_x, int out_format) {
+    constexpr int kFmt = RT_FORMAT_HIT;
+#include "rt_trace3_body.inc"
 }
 
 
@@ -2013,7 +1860,7 @@ __global__ void __launch_bounds__(64 * kSplitMax) RT_TRACE_ATTR trace3_split_ker
             const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
             if (xj < width && y < row_end)
                 store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
+                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
                                                 dir));
         }
         return;
@@ -2217,7 +2064,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
             const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
             if (xj < width && y < row_end)
                 store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
+                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
                                                 dir));
         }
         return;
@@ -2356,7 +2203,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
             const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
             if (xj < width && y < row_end)
                 store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
+                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
                                                 dir));
         }
         return;
@@ -2583,7 +2430,7 @@ __global__ void __launch_bounds__(64 * kFusedWaves) RT_FUSED_ATTR frame_small_ke
             const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
             if (xj < width && y < row_end)
                 store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
+                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
                                                 dir));
         }
         return;
@@ -2745,24 +2592,34 @@ int preload() {
     one(preload_one(coarse3_kernel<8>));
     one(preload_one(trace3_kernel<0, RT_FORMAT_I32X4>));
     one(preload_one(trace3_kernel<0, RT_FORMAT_RGBA8>));
+    one(preload_one(trace3_hit_kernel<0>));
     one(preload_one(trace3_split_kernel<RT_FORMAT_I32X4>));
     one(preload_one(trace3_split_kernel<RT_FORMAT_RGBA8>));
+    one(preload_one(trace3_split_kernel<RT_FORMAT_HIT>));
     one(preload_one(trace_bin_kernel<RT_FORMAT_I32X4>));
     one(preload_one(trace_bin_kernel<RT_FORMAT_RGBA8>));
+    one(preload_one(trace_bin_kernel<RT_FORMAT_HIT>));
     one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, 1>));
     one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, 1>));
+    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, 1>));
     one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, 2>));
     one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, 2>));
+    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, 2>));
     one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, 4>));
     one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, 4>));
+    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, 4>));
     one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, RT_SMALL_CHUNKS>));
     one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, RT_SMALL_CHUNKS>));
+    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, RT_SMALL_CHUNKS>));
     one(preload_one(frame_small_kernel<RT_FORMAT_I32X4, 1>));
     one(preload_one(frame_small_kernel<RT_FORMAT_RGBA8, 1>));
+    one(preload_one(frame_small_kernel<RT_FORMAT_HIT, 1>));
     one(preload_one(frame_small_kernel<RT_FORMAT_I32X4, 2>));
     one(preload_one(frame_small_kernel<RT_FORMAT_RGBA8, 2>));
+    one(preload_one(frame_small_kernel<RT_FORMAT_HIT, 2>));
     one(preload_one(frame_small_kernel<RT_FORMAT_I32X4, RT_FUSED_CHUNKS>));
     one(preload_one(frame_small_kernel<RT_FORMAT_RGBA8, RT_FUSED_CHUNKS>));
+    one(preload_one(frame_small_kernel<RT_FORMAT_HIT, RT_FUSED_CHUNKS>));
     return rc;
 }
 
@@ -2790,6 +2647,13 @@ int copy_verdict(rt_ctx* ctx, hipStream_t stream) {
     return enqueue_verdict_copy(ctx, stream);
 }
 
+// KERNEL<format, n> of launch()'s `fmt` (checked by the callers: one of the
+// three formats).
+#undef RT_BY_FMT
+#define RT_BY_FMT(KERNEL, N)                                  \
+    (fmt == RT_FORMAT_I32X4 ? KERNEL<RT_FORMAT_I32X4, N>      \
+     : fmt == RT_FORMAT_HIT ? KERNEL<RT_FORMAT_HIT, N>        \
+                            : KERNEL<RT_FORMAT_RGBA8, N>)
 // Enqueue one render of rows [row_begin, row_end) on `stream`.  All scene
 // pointers are device pointers.
 int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origins,
@@ -2812,7 +2676,7 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
         const int64_t per =
             band_rows_of(ctx, 12 * (int64_t)s->num_cubes + s->num_spheres, width, rows);
         if (per < rows) {
-            const size_t px_bytes = fmt == RT_FORMAT_I32X4 ? 16 : 4;
+            const size_t px_bytes = rt_args::pixel_bytes(fmt);
             const int32_t prof_count0 = ctx->prof_count;
             for (int64_t rb = row_begin; rb < row_end; rb += per) {
                 const int32_t re = (int32_t)std::min<int64_t>(rb + per, row_end);
@@ -2893,14 +2757,10 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
         ctx->trace_mode == 0 &&
         (ctx->small_fused == 2 || fused_wgs <= (int64_t)ctx->n_cu * (n_chunks == 1 ? 8 : 5))) {
         if ((rc = skip_k(ctx, pe_prep)) || (rc = skip_k(ctx, pe_coarse))) return rc;
-        const bool i32 = fmt == RT_FORMAT_I32X4;
-        auto fused = n_chunks == 1   ? (i32 ? frame_small_kernel<RT_FORMAT_I32X4, 1>
-                                            : frame_small_kernel<RT_FORMAT_RGBA8, 1>)
+        auto fused = n_chunks == 1 ? RT_BY_FMT(frame_small_kernel, 1)
                      : n_chunks == 2 || RT_FUSED_CHUNKS <= 2
-                         ? (i32 ? frame_small_kernel<RT_FORMAT_I32X4, 2>
-                                : frame_small_kernel<RT_FORMAT_RGBA8, 2>)
-                         : (i32 ? frame_small_kernel<RT_FORMAT_I32X4, RT_FUSED_CHUNKS>
-                                : frame_small_kernel<RT_FORMAT_RGBA8, RT_FUSED_CHUNKS>);
+                         ? RT_BY_FMT(frame_small_kernel, 2)
+                         : RT_BY_FMT(frame_small_kernel, RT_FUSED_CHUNKS);
         ctx->last_kernel = RT_KERNEL_FRAME_SMALL;
         return launch_k(fused, dim3((unsigned)(n_coarse64 * (kTiles / kFusedWaves))),
                         dim3(64 * kFusedWaves), stream, kernel_events(ctx, pe_trace, true, true), sd, dir, n_cx, width, row_begin,
@@ -2914,16 +2774,11 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
         if (rc) return rc;
         if ((rc = skip_k(ctx, pe_coarse))) return rc;
         // the instance with the fewest chunk slots that holds n_chunks
-        const bool i32 = fmt == RT_FORMAT_I32X4;
-        auto small = n_chunks == 1   ? (i32 ? trace_small_kernel<RT_FORMAT_I32X4, 1>
-                                            : trace_small_kernel<RT_FORMAT_RGBA8, 1>)
-                     : n_chunks == 2 ? (i32 ? trace_small_kernel<RT_FORMAT_I32X4, 2>
-                                            : trace_small_kernel<RT_FORMAT_RGBA8, 2>)
+        auto small = n_chunks == 1   ? RT_BY_FMT(trace_small_kernel, 1)
+                     : n_chunks == 2 ? RT_BY_FMT(trace_small_kernel, 2)
                      : n_chunks <= 4 || RT_SMALL_CHUNKS <= 4
-                         ? (i32 ? trace_small_kernel<RT_FORMAT_I32X4, 4>
-                                : trace_small_kernel<RT_FORMAT_RGBA8, 4>)
-                         : (i32 ? trace_small_kernel<RT_FORMAT_I32X4, RT_SMALL_CHUNKS>
-                                : trace_small_kernel<RT_FORMAT_RGBA8, RT_SMALL_CHUNKS>);
+                         ? RT_BY_FMT(trace_small_kernel, 4)
+                         : RT_BY_FMT(trace_small_kernel, RT_SMALL_CHUNKS);
         ctx->last_kernel = RT_KERNEL_TRACE_SMALL;
         return launch_k(small, dim3((unsigned)(n_coarse64 * kTiles)), dim3(64), stream, kernel_events(ctx, pe_trace, true, true),
                         (const unsigned long long*)row_masks, (const unsigned long long*)col_masks,
@@ -2946,7 +2801,8 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
     // above the split-trace sizes whose last binned frame on this context
     // had a box overdraw below the format's threshold (the coarse kernel's
     // depth culls then save less than the kernel costs; RGBA8 frames, bound
-    // by their tests, keep the triangle cull from a lower overdraw on)
+    // by their tests, keep the triangle cull from a lower overdraw on; HIT
+    // frames measured on RGBA8's side of int32x4's threshold: DESIGN.md §3.5)
     const int64_t n_tiles_all = n_coarse64 * kTiles;
     const bool bin_ok = n_prims > 0 && n_prims <= kBinCap && use_masks && ctx->trace_mode == 0;
     const unsigned verdict =
@@ -2966,6 +2822,7 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
         if (rc) return rc;
         if ((rc = skip_k(ctx, pe_coarse))) return rc;
         auto bk = fmt == RT_FORMAT_I32X4 ? trace_bin_kernel<RT_FORMAT_I32X4>
+                  : fmt == RT_FORMAT_HIT ? trace_bin_kernel<RT_FORMAT_HIT>
                                          : trace_bin_kernel<RT_FORMAT_RGBA8>;
         ctx->last_kernel = RT_KERNEL_TRACE_BIN;
         rc = launch_k(bk, dim3((unsigned)(n_cx * kTiles), (unsigned)n_cy), dim3(64), stream,
@@ -2993,12 +2850,15 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
         unsigned long long* od_word = reinterpret_cast<unsigned long long*>(ctx->flag + 2 + 2 * od_slot);
         unsigned long long* od_next = reinterpret_cast<unsigned long long*>(ctx->flag + 4 - 2 * od_slot);
         const unsigned long long od_min =
-            (fmt == RT_FORMAT_RGBA8 ? ctx->coarse_cull_overdraw_rgba8 : ctx->coarse_cull_overdraw) *
+            (fmt == RT_FORMAT_RGBA8 ? ctx->coarse_cull_overdraw_rgba8
+             : fmt == RT_FORMAT_HIT ? ctx->coarse_cull_overdraw_hit
+                                    : ctx->coarse_cull_overdraw) *
             area_units;
         // triangles join the depth cull only in bands of enough coarse bins
         // (rt_device.hip, RT_COARSE_CULL_TRI_BINS)
         const int cull_tri = n_coarse64 < ctx->coarse_cull_tri_bins ? 0
                              : fmt == RT_FORMAT_RGBA8          ? ctx->coarse_cull_tri_rgba8
+                             : fmt == RT_FORMAT_HIT            ? ctx->coarse_cull_tri_hit
                                                                : ctx->coarse_cull_tri;
         rc = skip_prep ? skip_k(ctx, pe_prep)
                        : launch_k(prep_kernel, dim3((unsigned)n_chunks), dim3(kPrepThreads), stream,
@@ -3043,6 +2903,12 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
                        : ctx->trace_mode == 3 ? trace3_kernel<3, RT_FORMAT_I32X4>
                        : ctx->trace_mode == 4 ? trace3_kernel<4, RT_FORMAT_I32X4>
                                               : trace3_kernel<0, RT_FORMAT_I32X4>)
+                : fmt == RT_FORMAT_HIT
+                    ? (ctx->trace_mode == 1   ? trace3_hit_kernel<1>
+                       : ctx->trace_mode == 2 ? trace3_hit_kernel<2>
+                       : ctx->trace_mode == 3 ? trace3_hit_kernel<3>
+                       : ctx->trace_mode == 4 ? trace3_hit_kernel<4>
+                                              : trace3_hit_kernel<0>)
                     : (ctx->trace_mode == 1   ? trace3_kernel<1, RT_FORMAT_RGBA8>
                        : ctx->trace_mode == 2 ? trace3_kernel<2, RT_FORMAT_RGBA8>
                        : ctx->trace_mode == 3 ? trace3_kernel<3, RT_FORMAT_RGBA8>
@@ -3050,6 +2916,7 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
                                               : trace3_kernel<0, RT_FORMAT_RGBA8>);
 #else
     auto kern = fmt == RT_FORMAT_I32X4 ? trace3_kernel<0, RT_FORMAT_I32X4>
+                : fmt == RT_FORMAT_HIT ? trace3_hit_kernel<0>
                                        : trace3_kernel<0, RT_FORMAT_RGBA8>;
 #endif
     const dim3 trace_grid((unsigned)(n_cx * kTiles), (unsigned)n_cy);
@@ -3065,6 +2932,7 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
     if (split > 1 && ctx->trace_mode == 0) {
         ctx->last_kernel = RT_KERNEL_TRACE_SPLIT;
         auto sk = fmt == RT_FORMAT_I32X4 ? trace3_split_kernel<RT_FORMAT_I32X4>
+                  : fmt == RT_FORMAT_HIT ? trace3_split_kernel<RT_FORMAT_HIT>
                                          : trace3_split_kernel<RT_FORMAT_RGBA8>;
         rc = launch_k(sk, trace_grid, dim3(64 * split), stream,
                         kernel_events(ctx, pe_trace, true, true), sd, (const TriRec*)tri,

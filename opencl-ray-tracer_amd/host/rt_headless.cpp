@@ -10,8 +10,8 @@
 //   rt_headless [--scene 1|2|3] [--seed S] [--width W] [--height H]
 //               [--synthetic N M k] [--rows A B] [--ppm out.ppm] [--repeat R]
 //               [--bands B] [--devices D] [--device-scene]
-//               [--format i32x4|rgba8] [--throughput F [--inflight S]]
-//               [--known-answer]
+//               [--format i32x4|rgba8|hit] [--throughput F [--inflight S]]
+//               [--known-answer] [--pick X,Y]
 //
 // --known-answer (reference scene 1, 2 or 3, 640x480, int32x4, the whole
 // frame, seed 1): checks the frame against the reference's own CPU frame as
@@ -25,6 +25,15 @@
 // (INTEGRATION.md), replacing the per-pixel SDL_FillRect loop; here the PPM
 // dump reads it the same way.  The printed hash is FNV-1a-64 over the uint32
 // words.
+//
+// --format hit asks for what the trace found instead of its colour
+// (RT_FORMAT_HIT: one rt_hit per pixel, the float `closest` of the collide
+// loop, MainState.cpp:330-394, and the winning object; a miss is 300000 and
+// -1).  The printed hash runs over the frame's 32-bit words (two per pixel);
+// --ppm shades the hit frame on the host with rt_shade_hits and writes the
+// same bytes as the int32x4 frame's PPM.  --pick X,Y (hit frames; frame
+// coordinates, inside the rendered rows) prints that pixel's object and t:
+// what is under the mouse.
 //
 // --device-scene (with --synthetic, one band) builds the scene on the GPU
 // with rt_scene_synthetic_device, renders it with
@@ -96,6 +105,12 @@ bool write_ppm(const std::string& path, const std::vector<int32_t>& frame, int w
     return true;
 }
 
+// 32-bit words per pixel, and the name, of a format
+size_t fmt_words(int32_t fmt) { return fmt == RT_FORMAT_I32X4 ? 4 : fmt == RT_FORMAT_HIT ? 2 : 1; }
+const char* fmt_name(int32_t fmt) {
+    return fmt == RT_FORMAT_I32X4 ? "i32x4" : fmt == RT_FORMAT_HIT ? "hit" : "rgba8";
+}
+
 struct Band {
     int device = 0, row_begin = 0, row_end = 0;
     rt_ctx* ctx = nullptr;
@@ -155,7 +170,7 @@ int throughput(int device, int width, int height, int n, int m, unsigned seed, f
     const size_t n4 = 4 * sizeof(float) * (size_t)(n > 0 ? n : 1);
     const size_t m4 = 4 * sizeof(float) * (size_t)(m > 0 ? m : 1);
     const size_t px = (size_t)width * height;
-    const size_t frame_words = (fmt == RT_FORMAT_RGBA8 ? 1 : 4) * px;
+    const size_t frame_words = fmt_words(fmt) * px;
     std::vector<rt_ctx*> ctx((size_t)slots, nullptr);
     std::vector<hipStream_t> st((size_t)slots, nullptr);
     std::vector<int32_t*> out((size_t)slots, nullptr);
@@ -219,8 +234,7 @@ int throughput(int device, int width, int height, int n, int m, unsigned seed, f
         std::vector<int32_t> host(frame_words);
         std::printf("throughput %dx%d spheres %d cubes %d %s: %d frames, %d in flight: "
                     "%.2f us per frame, %.1f Grays/s\n",
-                    width, height, n, m, fmt == RT_FORMAT_RGBA8 ? "rgba8" : "i32x4", frames,
-                    slots, us, (double)px / us / 1e3);
+                    width, height, n, m, fmt_name(fmt), frames, slots, us, (double)px / us / 1e3);
         ok = true;
         for (int i = 0; i < slots && ok; ++i) {
             ok = hipMemcpy(host.data(), out[(size_t)i], frame_words * sizeof(int32_t),
@@ -258,6 +272,7 @@ int main(int argc, char** argv) {
     int tp_frames = 0, tp_slots = 2;
     int32_t fmt = RT_FORMAT_I32X4;
     bool known_answer = false;
+    int pick_x = -1, pick_y = -1;
     std::string ppm;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -291,8 +306,15 @@ int main(int argc, char** argv) {
             const std::string v = next();
             if (v == "i32x4") fmt = RT_FORMAT_I32X4;
             else if (v == "rgba8") fmt = RT_FORMAT_RGBA8;
+            else if (v == "hit") fmt = RT_FORMAT_HIT;
             else {
-                std::fprintf(stderr, "--format takes i32x4 or rgba8\n");
+                std::fprintf(stderr, "--format takes i32x4, rgba8 or hit\n");
+                return 2;
+            }
+        }
+        else if (a == "--pick") {
+            if (std::sscanf(next(), "%d,%d", &pick_x, &pick_y) != 2 || pick_x < 0 || pick_y < 0) {
+                std::fprintf(stderr, "--pick takes X,Y\n");
                 return 2;
             }
         }
@@ -312,6 +334,11 @@ int main(int argc, char** argv) {
                          fmt != RT_FORMAT_I32X4)) {
         std::fprintf(stderr, "--known-answer needs --scene 1|2|3 at 640x480, seed 1, int32x4, "
                              "the whole frame\n");
+        return 2;
+    }
+    if (pick_x >= 0 && (fmt != RT_FORMAT_HIT || pick_x >= width || pick_y < row_begin ||
+                        pick_y >= row_end)) {
+        std::fprintf(stderr, "--pick needs --format hit and a pixel of the rendered rows\n");
         return 2;
     }
     if (device_scene && (syn_n < 0 || n_bands != 1)) {
@@ -375,9 +402,9 @@ int main(int argc, char** argv) {
     rt_primary_ray_dir(ray_dir);  // (0,0,-1,-1), MainState.cpp:37-39
     rt_scene scene{so.data(), sr.data(), sc.data(), ns, cv.data(), cc.data(), nc, nullptr, 0};
     // MainState::pixels (MainState.h:86, reserved at :215): 4 ints per pixel,
-    // or the Texture's one RGBA8 word per pixel
+    // the Texture's one RGBA8 word per pixel, or an rt_hit's two words
     const bool rgba8 = fmt == RT_FORMAT_RGBA8;
-    std::vector<int32_t> pixels((rgba8 ? 1 : 4) * (size_t)width * rows);
+    std::vector<int32_t> pixels(fmt_words(fmt) * (size_t)width * rows);
     if (device_scene) return render_device_scene(bands[0], width, height, row_begin, row_end,
                                                  syn_n, syn_m, seed, syn_k, ray_dir, fmt, pixels);
     // rt_render_multi: one host thread and one context per band, each band's
@@ -411,10 +438,29 @@ int main(int argc, char** argv) {
     }
     if (status == 0) {
         std::printf("frame %dx%d rows [%d,%d) spheres %d cubes %d %s fnv1a64 %016llx\n", width,
-                    height, row_begin, row_end, ns, nc, rgba8 ? "rgba8" : "i32x4",
+                    height, row_begin, row_end, ns, nc, fmt_name(fmt),
                     (unsigned long long)fnv1a(pixels.data(), pixels.size()));
-        if (!ppm.empty() && !write_ppm(ppm, pixels, width, rows, rgba8))
-            std::fprintf(stderr, "could not write %s\n", ppm.c_str());
+        if (pick_x >= 0) {
+            rt_hit h;
+            std::memcpy(&h, &pixels[2 * ((size_t)(pick_y - row_begin) * width + pick_x)], sizeof h);
+            // (%.9g: enough digits to give the float back exactly)
+            std::printf("pick %d,%d object %d t %.9g\n", pick_x, pick_y, (int)h.object,
+                        (double)h.t);
+        }
+        if (!ppm.empty()) {
+            bool ok;
+            if (fmt == RT_FORMAT_HIT) {
+                // the image the int32x4 frame would have given
+                std::vector<int32_t> shaded(4 * (size_t)width * rows);
+                ok = rt_shade_hits(reinterpret_cast<const rt_hit*>(pixels.data()),
+                                   (int64_t)width * rows, &scene, RT_FORMAT_I32X4,
+                                   shaded.data()) == RT_OK &&
+                     write_ppm(ppm, shaded, width, rows, false);
+            } else {
+                ok = write_ppm(ppm, pixels, width, rows, rgba8);
+            }
+            if (!ok) std::fprintf(stderr, "could not write %s\n", ppm.c_str());
+        }
         if (known_answer) {
             const uint64_t got = fnv1a(pixels.data(), pixels.size(), kProbeBasis);
             const uint64_t want = kKnownAnswer[scene_id - 1];

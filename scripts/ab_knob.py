@@ -72,7 +72,7 @@ def main():
                     help="a RayTracer setter without set_ (coarse_cull, trace_bin, trace_bin_cull, ...)")
     ap.add_argument("--values", default="0,1")
     ap.add_argument("--configs", default="c3,c5d,c5s,band8")
-    ap.add_argument("--format", default="i32x4", choices=("i32x4", "rgba8"))
+    ap.add_argument("--format", default="i32x4", choices=("i32x4", "rgba8", "hit"))
     ap.add_argument("--fixed", action="append", default=[],
                     help="knob=value held for every setting (repeatable)")
     ap.add_argument("--rounds", type=int, default=7)
@@ -106,7 +106,7 @@ def main():
                        "cube_colours")}
         ds = {n: v.data_ptr() for n, v in t.items()}
         ds.update(num_spheres=ns, num_cubes=nc)
-        shape = (re - rb, w, 4) if args.format == "i32x4" else (re - rb, w)
+        shape = (re - rb, w, {"i32x4": 4, "hit": 2, "rgba8": 1}[args.format])
         out = torch.empty(shape, dtype=torch.int32, device=dev)
         step = rt.bind_render_device(ds, w, h, (rb, re), out.data_ptr(), fmt=args.format,
                                      stream=stream.cuda_stream)
