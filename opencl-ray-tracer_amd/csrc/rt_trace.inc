@@ -15,6 +15,15 @@
 // Every pixel-writing kernel exists per output format (kFmt): int32x4, the
 // Texture's RGBA8 word, or RT_FORMAT_HIT (rt_hit: the walk's closest and
 // colour slot, unshaded).
+
+// Compile-time experiments that were measured, decided and removed
+// (DESIGN.md §3.5).  A stale recipe passing one of them must not silently
+// build, and "measure", the default.
+#if defined(RT_WALK_BALLOT) || defined(RT_WALK_BALLOT_SPLIT) || defined(RT_BIN_ABLATE) ||    \
+    defined(RT_EXTRA_VALU) || defined(RT_EXTRA_SALU) || defined(RT_REC_U32) ||               \
+    defined(RT_PREP_TRIDEPTH) || defined(RT_PREP_OVERDRAW) || defined(RT_DEPTH_CULL)
+#error "RT_WALK_BALLOT, RT_WALK_BALLOT_SPLIT, RT_BIN_ABLATE, RT_EXTRA_VALU, RT_EXTRA_SALU, RT_REC_U32, RT_PREP_TRIDEPTH, RT_PREP_OVERDRAW and RT_DEPTH_CULL were decided and removed (DESIGN.md §3.5); their code is in history, last at commit 9cad428"
+#endif
 namespace {
 
 // Build-time geometry / feature knobs (A/B variants: scripts/variants.sh).
@@ -624,15 +633,6 @@ __device__ __forceinline__ unsigned long long wave_suffix_or64(unsigned long lon
 #ifndef RT_BIN_DROP
 #define RT_BIN_DROP 1  // depth cull: bin-level lower bound before the tile-local ones
 #endif
-#ifndef RT_PREP_TRIDEPTH
-#define RT_PREP_TRIDEPTH 1  // diagnostics: 0 skips the TriDepth models (triangle cull must be off)
-#endif
-#ifndef RT_PREP_OVERDRAW
-#define RT_PREP_OVERDRAW 1  // diagnostics: 0 skips the box-overdraw sum
-#endif
-#if !RT_DIAG && (!RT_PREP_TRIDEPTH || !RT_PREP_OVERDRAW)
-#error "RT_PREP_TRIDEPTH=0 / RT_PREP_OVERDRAW=0 are diagnostics: build with RT_DIAG=1"
-#endif
 __global__ void __launch_bounds__(kPrepThreads) prep_kernel(
     SceneDev scene, float4 dir, int width, int row_begin, int row_end,
     TriRec* __restrict__ tri, TriDepth* __restrict__ tdep, SphRec* __restrict__ sph,
@@ -656,9 +656,9 @@ __global__ void __launch_bounds__(kPrepThreads) prep_kernel(
         TriRec r{};
         TriDepth dd{0.0, 0.0, 0.0, INFINITY, 0.0, 0.0};
         prep_triangle(fa, fb, fc, (double)dir.x, (double)dir.y, (double)dir.z, width, row_begin,
-                      row_end, &r, &b, &k, &bad, RT_PREP_TRIDEPTH ? &dd : nullptr);
+                      row_end, &r, &b, &k, &bad, &dd);
         tri[i] = r;
-        if (RT_PREP_TRIDEPTH) tdep[i] = dd;
+        tdep[i] = dd;
     } else if (i < n_prims) {
         const int s = i - n_tri;
         const float4 o = scene.sphere_origins[s];
@@ -674,7 +674,7 @@ __global__ void __launch_bounds__(kPrepThreads) prep_kernel(
         cls[i] = k;
         if (bad) atomicMax(nonfinite_flag, gen);
     }
-    if (RT_PREP_OVERDRAW && overdraw) {
+    if (overdraw) {
         // the frame's box overdraw for the coarse kernel's triangle gate: the
         // sum of the boxes' areas in units of 64 pixels, one atomic add per
         // wave (coarse zeroes the other slot for the next launch)
@@ -736,24 +736,18 @@ __device__ __forceinline__ unsigned rt_now() { return (unsigned)__builtin_amdgcn
 #define TL_MARK(v)
 #endif
 
-// A candidate's record (wave-uniform index, 0 <= i < 2^25).  RT_REC_U32:
-// addressed by a 32-bit byte offset (one s_lshl_b32, then the 64-bit add)
-// instead of the sign extension and 64-bit shift of base[i], shortening the
-// scalar chain in front of each record's load.
-#ifndef RT_REC_U32
-#define RT_REC_U32 1  // round 6: kernels 0.2-1 % faster, DESIGN.md §3.5
-#endif
+// A candidate's record (wave-uniform index, 0 <= i < 2^25), addressed by a
+// 32-bit byte offset (one s_lshl_b32, then the 64-bit add) instead of the
+// sign extension and 64-bit shift of base[i], shortening the scalar chain in
+// front of each record's load (round 6: kernels 0.2-1 % faster, DESIGN.md
+// §3.5).
 __device__ __forceinline__ TriRec tri_at(const TriRec* __restrict__ base, int i) {
-    if constexpr (RT_REC_U32 != 0)
-        return *reinterpret_cast<const TriRec*>(reinterpret_cast<const char*>(base) +
-                                                ((unsigned)i << 7));
-    return base[i];
+    return *reinterpret_cast<const TriRec*>(reinterpret_cast<const char*>(base) +
+                                            ((unsigned)i << 7));
 }
 __device__ __forceinline__ SphRec sph_at(const SphRec* __restrict__ base, int i) {
-    if constexpr (RT_REC_U32 != 0)
-        return *reinterpret_cast<const SphRec*>(reinterpret_cast<const char*>(base) +
-                                                ((unsigned)i << 5));
-    return base[i];
+    return *reinterpret_cast<const SphRec*>(reinterpret_cast<const char*>(base) +
+                                            ((unsigned)i << 5));
 }
 
 // The overdraw verdict word (rt_ctx::od_verdict): one lane's vector store at
@@ -1735,32 +1729,20 @@ __global__ void __launch_bounds__(64 * kW) RT_COARSE_ATTR coarse3_kernel(
 #define RT_TRACE_ATTR
 #endif
 
-#ifndef RT_DEPTH_CULL
-#define RT_DEPTH_CULL 1  // skip spheres that cannot beat any lane's closest
-#endif
-// The candidate walk by keep ballots (the bin's list as vector loads, 64
-// entries a round, only the entries this tile keeps visited; see
-// trace3_kernel) instead of scalar batches of 8 with every entry's keep bit
-// tested.  Round 6, interleaved A/B (DESIGN.md §3.5): the small-frame split
-// trace 11.9 -> 9.4 us (reference scene 3 at 640x480), so it is on there;
-// the full-size trace3_kernel flat (RGBA8 config 3 27.84 / 27.87 us) to
-// slower (int32x4 43.4 -> 44.1, config 5 dense RGBA8 366 -> 395), so off.
-#ifndef RT_WALK_BALLOT
-#define RT_WALK_BALLOT 0  // trace3_kernel
-#endif
-#ifndef RT_WALK_BALLOT_SPLIT
-#define RT_WALK_BALLOT_SPLIT 1  // trace3_split_kernel
-#endif
-#ifndef RT_EXTRA_VALU
-#define RT_EXTRA_VALU 0  // diagnostics only: see trace3_kernel
-#endif
-#ifndef RT_EXTRA_SALU
-#define RT_EXTRA_SALU 0  // diagnostics only: see trace3_kernel
-#endif
+// Two candidate walks (round 6, interleaved A/B, DESIGN.md §3.5).
+// trace3_kernel reads the bin's list in scalar batches of 8 and tests every
+// entry's keep bit; trace3_split_kernel loads it as vectors, 64 entries a
+// round, and visits only the entries its tile keeps (one keep ballot).  The
+// ballot walk won on the small-frame split trace (11.9 -> 9.4 us, reference
+// scene 3 at 640x480) and was flat to slower in the full-size trace3_kernel
+// (int32x4 43.4 -> 44.1 us, config 5 dense RGBA8 366 -> 395).
 
-// Wave-uniform order_key of the largest closest[] of the wave: per-lane max
-// over its rows, then a DPP max to lane 63 (row_shr 1/2/4/8 within rows of
-// 16, row_bcast 15/31 across them; shifted-in lanes read 0, the identity).
+// The walk's sphere depth cull: a sphere whose lower bound (SphRec::tmin_key)
+// no lane's closest exceeds cannot be taken by any lane (strict <), so it is
+// skipped.  The bound, refreshed lazily by each walk, is the wave-uniform
+// order_key of the largest closest[] of the wave: per-lane max over its rows,
+// then a DPP max to lane 63 (row_shr 1/2/4/8 within rows of 16, row_bcast
+// 15/31 across them; shifted-in lanes read 0, the identity).
 __device__ __forceinline__ unsigned wave_max_key(const float* closest) {
     float m = closest[0];
 #pragma unroll
@@ -1785,33 +1767,152 @@ __device__ __forceinline__ unsigned wave_max_key(const float* closest) {
 // per wave, the triangle record in one round of scalar loads
 // (both round-4 knobs: profiles/r04/trace_variants.patch), an XCD-contiguous
 // tile order, the first
-// list batch loaded beside the count, a store hand-off through LDS.)
+// list batch loaded beside the count, a store hand-off through LDS, the
+// keep-ballot walk of trace3_split_kernel here, with and without the list's
+// first 64 entries loaded beside the count; last in 9cad428.)
 static_assert((kTiles & (kTiles - 1)) == 0, "tiles per bin: a power of two");
 // (Arguments in the order the wave needs them: with kernel-argument
 // preloading the first 14 dwords arrive in SGPRs.)
-// (The body is rt_trace3_body.inc, included into the kernel's two entry
-// points: the same text, so the same code, under two names.)
+// Every output format is an instance of this one template; kMode != 0 (the
+// trace ablations of rt_debug_set_trace_mode) exists in RT_DIAG builds only.
 template <int kMode, int kFmt>
 __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_kernel(
     const int* __restrict__ counts, const int* __restrict__ lists,
     const TriRec* __restrict__ tri, const SphRec* __restrict__ sph, int n_cx, int half_cap,
     int width, int row_begin, int row_end, int n_cubes, const float4* __restrict__ colours,
     void* __restrict__ out, SceneDev scene, float4 dir, int n_tiles_x, int out_format) {
-#include "rt_trace3_body.inc"
-}
+    // (unsigned: the divisions by powers of two are shifts and masks)
+    const unsigned bid = blockIdx.x;
+    const int cbx = (int)(bid / kTiles), cby = (int)blockIdx.y;
+    const int cb = cby * n_cx + cbx;
+    const unsigned t = bid % kTiles;  // the tile of the bin (wave-uniform)
+#if RT_TIMELINE
+    const int tile = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
+#endif
+    const int lane = threadIdx.x & 63;
+    const int n_tri = 12 * n_cubes;
+    (void)n_tiles_x;
+    (void)out_format;
+    TL_MARK(tl0);
+#if RT_TIMELINE
+    const unsigned long long tlc0 = __builtin_amdgcn_s_memtime();
+    unsigned tl1 = 0, tl2 = 0;
+#endif
+    const int rel_x = cbx * kCoarseW + (int)(t % kTilesX) * kWaveTile;
+    const int rel_y = cby * kCoarseH + (int)(t / kTilesX) * kWaveTileH;  // vs row_begin
+    const int tile_x = rel_x, tile_y = row_begin + rel_y;
+    const int x = tile_x + (lane % kLanesX);  // the lane's pixel 0
+    const int y0 = tile_y + (lane / kLanesX);
+    // wave-uniform: tiles past the frame's right or bottom edge render nothing
+    const bool tile_in = rel_x < width && rel_y < row_end - row_begin;
 
-// The RT_FORMAT_HIT instance under a name of its own: the library's
-// trace3_kernel<mode, format> symbols stay the two colour formats' (the
-// shipped build has exactly <0, int32x4> and <0, RGBA8>; tests/test_capi.py
-// counts them to prove that no ablation mode is compiled in).
-template <int kMode>
-__global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_hit_kernel(
-    const int* __restrict__ counts, const int* __restrict__ lists,
-    const TriRec* __restrict__ tri, const SphRec* __restrict__ sph, int n_cx, int half_cap,
-    int width, int row_begin, int row_end, int n_cubes, const float4* __restrict__ colours,
-    void* __restrict__ out, SceneDev scene, float4 dir, int n_tiles_x, int out_format) {
-    constexpr int kFmt = RT_FORMAT_HIT;
-#include "rt_trace3_body.inc"
+    // the bin's count (-1: non-finite scene data, see coarse3_kernel) is the
+    // wave's first data load
+    const int count_raw = kMode == 1 ? 0 : counts[cb];
+    if (tile_in && kMode == 0 && count_raw < 0) {
+        // Non-finite scene data: run the reference algorithm verbatim.
+#pragma unroll 1
+        for (int j = 0; j < kRowsPerLane; ++j) {
+            const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
+            if (xj < width && y < row_end)
+                store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
+                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
+                                                dir));
+        }
+    } else if (tile_in) {
+        int4v pix[kRowsPerLane];  // assigned after the walk (not live during it)
+        float closest[kRowsPerLane];
+        int hit[kRowsPerLane];
+        double px[kRowsPerLane], py[kRowsPerLane];
+        float pxf[kRowsPerLane], pyf[kRowsPerLane];
+#pragma unroll
+        for (int j = 0; j < kRowsPerLane; ++j) {
+            closest[j] = kFar;
+            hit[j] = -1;
+            py[j] = (double)(y0 + pix_dy(j));
+            pyf[j] = (float)(y0 + pix_dy(j));
+            px[j] = (double)(x + pix_dx(j));
+            pxf[j] = (float)(x + pix_dx(j));
+        }
+        // order_key of the largest `closest` in the tile, refreshed lazily
+        unsigned tile_max_key = order_key(kFar);
+        bool dirty = false;
+        const int count = count_raw < 0 ? 0 : count_raw;
+        const int* __restrict__ ids = lists + (int64_t)cb * kListStride * half_cap;
+        const int* __restrict__ tms = ids + (1 + (int)(t / kTilesPerWord)) * half_cap;  // its word
+        const int tm_shift = kTileBits * (int)(t % kTilesPerWord);
+#if RT_TIMELINE
+        tl1 = rt_now();
+#endif
+        for (int i0 = 0; i0 < count; i0 += 8) {
+            int idv[8], tmv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                idv[k] = ids[i0 + k];  // half_cap is a multiple of 8 past the count
+                tmv[k] = tms[i0 + k];
+            }
+            const int n = min(8, count - i0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (k >= n) break;
+                const unsigned bits = ((unsigned)tmv[k] >> tm_shift) & kTileMask;
+                if (!(bits & kKeepMask)) continue;
+                const int p = idv[k];
+                if (kMode == 2) {
+                    hit[0] = hit[0] > p ? hit[0] : -1;
+                    continue;
+                }
+                // both branches produce t per row (NaN: may not take); closest
+                // and hit are updated once, after them (round 4: trace 1-3 %
+                // faster than a test-and-update in each branch, DESIGN.md §3.5)
+                float tc[kRowsPerLane];
+                int slot;
+                if (p < n_tri) {
+                    const TriRec r = tri_at(tri, p);
+                    asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
+                    if constexpr (kRecomputeXY)
+                        tri_rows_fresh(r, bits, px[0], py[0], tc);
+                    else
+                        tri_rows(r, bits, px, py, tc);
+                    slot = p / 12;
+                } else {
+                    const SphRec r = sph_at(sph, p - n_tri);
+                    // t0 >= tmin >= every closest: no lane can take it (strict <)
+                    if (dirty) {
+                        tile_max_key = wave_max_key(closest);
+                        dirty = false;
+                    }
+                    if (r.tmin_key >= tile_max_key) continue;
+                    if constexpr (kRecomputeXY)
+                        sph_rows_fresh(r, bits, pxf[0], pyf[0], tc);
+                    else
+                        sph_rows(r, bits, pxf, pyf, tc);
+                    slot = n_cubes + (p - n_tri);
+                }
+                take_rows(tc, slot, closest, hit);
+                dirty = true;
+            }
+        }
+#if RT_TIMELINE
+        tl2 = rt_now();
+#endif
+        shade_pixels<kMode, kFmt>(colours, closest, hit, pix);
+        const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
+        store_rows<kMode, kFmt>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
+    }  // finite scene, tile inside the frame
+#if RT_TIMELINE
+    {
+        const unsigned tl3 = rt_now();
+        const unsigned long long tlc3 = __builtin_amdgcn_s_memtime();
+        if (lane == 0) {
+            unsigned* o = g_timeline + 8 * (int64_t)tile;
+            o[0] = tl0; o[1] = tl1; o[2] = tl2; o[3] = tl3;
+            o[4] = (unsigned)tlc0; o[5] = (unsigned)tlc3;
+            o[6] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
+            o[7] = __builtin_amdgcn_s_getreg((31 << 11) | 20);
+        }
+    }
+#endif
 }
 
 
@@ -1878,17 +1979,16 @@ __global__ void __launch_bounds__(64 * kSplitMax) RT_TRACE_ATTR trace3_split_ker
         px[j] = (double)(x + pix_dx(j));
         pxf[j] = (float)(x + pix_dx(j));
     }
-#if RT_DEPTH_CULL
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
-#endif
     const int* __restrict__ ids = lists + (int64_t)cb * kListStride * half_cap;
     const int* __restrict__ tms = ids + (1 + (int)(t / kTilesPerWord)) * half_cap;
     const int tm_shift = kTileBits * (int)(t % kTilesPerWord);
     int turn = 0;  // whose kept candidate is next: 0 .. n_waves - 1 (every wave counts all)
-#if RT_WALK_BALLOT_SPLIT
-    // (the list by vector loads and one keep ballot per 64 entries, as in
-    // trace3_kernel; every wave visits every kept entry to count turns)
+    // The bin's list 64 entries at a time as vector loads (entry e on lane
+    // e), this tile's keep bits in one ballot, and only the kept entries
+    // visited (s_ff1 over the mask, id and bits by v_readlane), in primitive
+    // order; every wave visits every kept entry to count turns.
     for (int c0 = 0; c0 < count_raw; c0 += 64) {
         const int e = c0 + lane;
         int idl = 0;
@@ -1915,66 +2015,18 @@ __global__ void __launch_bounds__(64 * kSplitMax) RT_TRACE_ATTR trace3_split_ker
                 slot = p / 12;
             } else {
                 const SphRec r = sph_at(sph, p - n_tri);
-#if RT_DEPTH_CULL
                 if (dirty) {
                     tile_max_key = wave_max_key(closest);
                     dirty = false;
                 }
                 if (r.tmin_key >= tile_max_key) continue;
-#endif
                 sph_rows(r, bits, pxf, pyf, tc);
                 slot = scene.n_cubes + (p - n_tri);
             }
             take_rows(tc, slot, closest, hit);
-#if RT_DEPTH_CULL
             dirty = true;
-#endif
         }
     }
-#else
-    for (int i0 = 0; i0 < count_raw; i0 += 8) {
-        int idv[8], tmv[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            idv[k] = ids[i0 + k];
-            tmv[k] = tms[i0 + k];
-        }
-        const int n = min(8, count_raw - i0);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (k >= n) break;
-            const unsigned bits = ((unsigned)tmv[k] >> tm_shift) & kTileMask;
-            if (!(bits & kKeepMask)) continue;
-            const bool mine = turn == wave;
-            turn = turn + 1 == n_waves ? 0 : turn + 1;
-            if (!mine) continue;
-            const int p = idv[k];
-            float tc[kRowsPerLane];
-            int slot;
-            if (p < n_tri) {
-                const TriRec r = tri_at(tri, p);
-                asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-                tri_rows(r, bits, px, py, tc);
-                slot = p / 12;
-            } else {
-                const SphRec r = sph_at(sph, p - n_tri);
-#if RT_DEPTH_CULL
-                if (dirty) {
-                    tile_max_key = wave_max_key(closest);
-                    dirty = false;
-                }
-                if (r.tmin_key >= tile_max_key) continue;
-#endif
-                sph_rows(r, bits, pxf, pyf, tc);
-                slot = scene.n_cubes + (p - n_tri);
-            }
-            take_rows(tc, slot, closest, hit);
-#if RT_DEPTH_CULL
-            dirty = true;
-#endif
-        }
-    }
-#endif
     // merge into wave 0: the other waves' closest / hit through LDS
     __shared__ float s_close[kSplitMax - 1][kRowsPerLane][64];
     __shared__ int s_hit[kSplitMax - 1][kRowsPerLane][64];
@@ -2108,10 +2160,8 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
         px[j] = (double)(x + pix_dx(j));
         pxf[j] = (float)(x + pix_dx(j));
     }
-#if RT_DEPTH_CULL
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
-#endif
 #pragma unroll
     for (int c = 0; c < kChunks; ++c)
     while (keep[c]) {  // kept candidates in primitive order
@@ -2128,20 +2178,16 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
             slot = p / 12;
         } else {
             const SphRec r = sph_at(sph, p - n_tri);
-#if RT_DEPTH_CULL
             if (dirty) {
                 tile_max_key = wave_max_key(closest);
                 dirty = false;
             }
             if (r.tmin_key >= tile_max_key) continue;
-#endif
             sph_rows(r, bits, pxf, pyf, tc);
             slot = n_cubes + (p - n_tri);
         }
         take_rows(tc, slot, closest, hit);
-#if RT_DEPTH_CULL
         dirty = true;
-#endif
     }
     shade_pixels<0, kFmt>(colours, closest, hit, pix);
     const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
@@ -2159,9 +2205,6 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
 // cull (a per-tile one measured slower, DESIGN.md §3.5); the walk's own
 // sphere cull stays.  Non-finite scene data: the reference verbatim.
 constexpr int kBinCap = 1024;  // trace_bin_kernel: scenes of at most this many primitives
-#ifndef RT_BIN_ABLATE
-#define RT_BIN_ABLATE 0
-#endif
 
 template <int kFmt>
 __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
@@ -2212,19 +2255,8 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
     // this kernel only for scenes of at most kBinCap primitives: they fit)
     __shared__ int s_ids[kBinCap];
     int n_cand = 0;
-#if RT_BIN_ABLATE
-    // diagnostics (frames wrong on purpose): 1 = no walk, 2 = no
-    // classification either, 3 = no mask loads either (stores only); 4 = the
-    // walk without the hit-colour gather; 5 = the walk's record loads
-    // without the exact tests (and so without the gather)
-    int abl_zero = 0;
-    asm volatile("" : "+s"(abl_zero));
-    const int abl_chunks = RT_BIN_ABLATE == 3 ? n_chunks * abl_zero : n_chunks;
-#else
-    const int abl_chunks = n_chunks;
-#endif
     {
-        const unsigned long long w = lane < abl_chunks ? rw[lane] & cw[lane] : 0ull;
+        const unsigned long long w = lane < n_chunks ? rw[lane] & cw[lane] : 0ull;
         unsigned long long nz = __ballot(w != 0ull);
         while (nz) {  // the nonzero chunks in order; their ids in bit order
             const int c = __builtin_ctzll(nz);
@@ -2242,9 +2274,6 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
     }
     __builtin_amdgcn_wave_barrier();
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
-#if RT_BIN_ABLATE == 2 || RT_BIN_ABLATE == 3
-    n_cand *= abl_zero;
-#endif
     // (2) classify them against this tile, 64 at a time, compacting the kept
     // ones in place (bit 31: u,v proven inside); a round's ids are read
     // before any of its writes, which land at or below its first slot
@@ -2273,9 +2302,6 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
         __builtin_amdgcn_wave_barrier();
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
     }
-#if RT_BIN_ABLATE >= 1 && RT_BIN_ABLATE <= 3
-    n_kept *= abl_zero;
-#endif
     // (3) walk the kept candidates in order, 8 entries per LDS read round
     float closest[kRowsPerLane];
     int hit[kRowsPerLane];
@@ -2290,10 +2316,8 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
         px[j] = (double)(x + pix_dx(j));
         pxf[j] = (float)(x + pix_dx(j));
     }
-#if RT_DEPTH_CULL
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
-#endif
     for (int i0 = 0; i0 < n_kept; i0 += 8) {
         const int ent = lane < 8 && i0 + lane < n_kept ? s_ids[i0 + lane] : 0;
         const int n = min(8, n_kept - i0);
@@ -2308,36 +2332,24 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
             if (p < n_tri) {
                 const TriRec r = tri_at(tri, p);
                 asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-#if RT_BIN_ABLATE == 5
-                asm volatile("" ::"s"(r.e1x), "s"(r.e2x), "s"(r.e1y));
-                continue;
-#endif
                 tri_rows(r, bits, px, py, tc);
                 slot = p / 12;
             } else {
                 const SphRec r = sph_at(sph, p - n_tri);
-#if RT_BIN_ABLATE == 5
-                asm volatile("" ::"s"(r.cx), "s"(r.cy), "s"(r.r2));
-                continue;
-#endif
-#if RT_DEPTH_CULL
                 if (dirty) {
                     tile_max_key = wave_max_key(closest);
                     dirty = false;
                 }
                 if (r.tmin_key >= tile_max_key) continue;
-#endif
                 sph_rows(r, bits, pxf, pyf, tc);
                 slot = scene.n_cubes + (p - n_tri);
             }
             take_rows(tc, slot, closest, hit);
-#if RT_DEPTH_CULL
             dirty = true;
-#endif
         }
     }
     int4v pix[kRowsPerLane];
-    shade_pixels<RT_BIN_ABLATE == 4 ? 4 : 0, kFmt>(colours, closest, hit, pix);
+    shade_pixels<0, kFmt>(colours, closest, hit, pix);
     const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
     store_rows<0, kFmt>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
 }
@@ -2462,10 +2474,8 @@ __global__ void __launch_bounds__(64 * kFusedWaves) RT_FUSED_ATTR frame_small_ke
         px[j] = (double)(x + pix_dx(j));
         pxf[j] = (float)(x + pix_dx(j));
     }
-#if RT_DEPTH_CULL
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
-#endif
 #pragma unroll
     for (int c = 0; c < kChunks; ++c)
     while (keep[c]) {  // kept candidates in primitive order
@@ -2483,20 +2493,16 @@ __global__ void __launch_bounds__(64 * kFusedWaves) RT_FUSED_ATTR frame_small_ke
             slot = p / 12;
         } else {
             const SphRec& r = s_sph[p - n_tri];
-#if RT_DEPTH_CULL
             if (dirty) {
                 tile_max_key = wave_max_key(closest);
                 dirty = false;
             }
             if (r.tmin_key >= tile_max_key) continue;
-#endif
             sph_rows(r, bits, pxf, pyf, tc);
             slot = scene.n_cubes + (p - n_tri);
         }
         take_rows(tc, slot, closest, hit);
-#if RT_DEPTH_CULL
         dirty = true;
-#endif
     }
     int4v pix[kRowsPerLane];
     shade_pixels<0, kFmt>(s_col, closest, hit, pix);
@@ -2581,6 +2587,12 @@ int preload_one(K kernel) {
                : RT_ERR_HIP;
 }
 
+// every output format's instance of KERNEL<format, ...>
+#undef RT_PRELOAD_FMTS
+#define RT_PRELOAD_FMTS(KERNEL, ...)                              \
+    one(preload_one(KERNEL<RT_FORMAT_I32X4, ##__VA_ARGS__>));     \
+    one(preload_one(KERNEL<RT_FORMAT_RGBA8, ##__VA_ARGS__>));     \
+    one(preload_one(KERNEL<RT_FORMAT_HIT, ##__VA_ARGS__>))
 int preload() {
     int rc = RT_OK;
     auto one = [&rc](int r) { if (r != RT_OK) rc = r; };
@@ -2592,34 +2604,16 @@ int preload() {
     one(preload_one(coarse3_kernel<8>));
     one(preload_one(trace3_kernel<0, RT_FORMAT_I32X4>));
     one(preload_one(trace3_kernel<0, RT_FORMAT_RGBA8>));
-    one(preload_one(trace3_hit_kernel<0>));
-    one(preload_one(trace3_split_kernel<RT_FORMAT_I32X4>));
-    one(preload_one(trace3_split_kernel<RT_FORMAT_RGBA8>));
-    one(preload_one(trace3_split_kernel<RT_FORMAT_HIT>));
-    one(preload_one(trace_bin_kernel<RT_FORMAT_I32X4>));
-    one(preload_one(trace_bin_kernel<RT_FORMAT_RGBA8>));
-    one(preload_one(trace_bin_kernel<RT_FORMAT_HIT>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, 1>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, 1>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, 1>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, 2>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, 2>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, 2>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, 4>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, 4>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, 4>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_I32X4, RT_SMALL_CHUNKS>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_RGBA8, RT_SMALL_CHUNKS>));
-    one(preload_one(trace_small_kernel<RT_FORMAT_HIT, RT_SMALL_CHUNKS>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_I32X4, 1>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_RGBA8, 1>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_HIT, 1>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_I32X4, 2>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_RGBA8, 2>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_HIT, 2>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_I32X4, RT_FUSED_CHUNKS>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_RGBA8, RT_FUSED_CHUNKS>));
-    one(preload_one(frame_small_kernel<RT_FORMAT_HIT, RT_FUSED_CHUNKS>));
+    one(preload_one(trace3_kernel<0, RT_FORMAT_HIT>));
+    RT_PRELOAD_FMTS(trace3_split_kernel);
+    RT_PRELOAD_FMTS(trace_bin_kernel);
+    RT_PRELOAD_FMTS(trace_small_kernel, 1);
+    RT_PRELOAD_FMTS(trace_small_kernel, 2);
+    RT_PRELOAD_FMTS(trace_small_kernel, 4);
+    RT_PRELOAD_FMTS(trace_small_kernel, RT_SMALL_CHUNKS);
+    RT_PRELOAD_FMTS(frame_small_kernel, 1);
+    RT_PRELOAD_FMTS(frame_small_kernel, 2);
+    RT_PRELOAD_FMTS(frame_small_kernel, RT_FUSED_CHUNKS);
     return rc;
 }
 
@@ -2647,13 +2641,18 @@ int copy_verdict(rt_ctx* ctx, hipStream_t stream) {
     return enqueue_verdict_copy(ctx, stream);
 }
 
-// KERNEL<format, n> of launch()'s `fmt` (checked by the callers: one of the
-// three formats).
+// KERNEL<format, ...> of launch()'s `fmt` (checked by the callers: one of
+// the three formats), and trace3_kernel<MODE, format>.
 #undef RT_BY_FMT
-#define RT_BY_FMT(KERNEL, N)                                  \
-    (fmt == RT_FORMAT_I32X4 ? KERNEL<RT_FORMAT_I32X4, N>      \
-     : fmt == RT_FORMAT_HIT ? KERNEL<RT_FORMAT_HIT, N>        \
-                            : KERNEL<RT_FORMAT_RGBA8, N>)
+#define RT_BY_FMT(KERNEL, ...)                                        \
+    (fmt == RT_FORMAT_I32X4 ? KERNEL<RT_FORMAT_I32X4, ##__VA_ARGS__>  \
+     : fmt == RT_FORMAT_HIT ? KERNEL<RT_FORMAT_HIT, ##__VA_ARGS__>    \
+                            : KERNEL<RT_FORMAT_RGBA8, ##__VA_ARGS__>)
+#undef RT_TRACE3_BY_FMT
+#define RT_TRACE3_BY_FMT(MODE)                                     \
+    (fmt == RT_FORMAT_I32X4 ? trace3_kernel<MODE, RT_FORMAT_I32X4> \
+     : fmt == RT_FORMAT_HIT ? trace3_kernel<MODE, RT_FORMAT_HIT>   \
+                            : trace3_kernel<MODE, RT_FORMAT_RGBA8>)
 // Enqueue one render of rows [row_begin, row_end) on `stream`.  All scene
 // pointers are device pointers.
 int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origins,
@@ -2821,9 +2820,7 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
                       row_masks, col_masks, n_cx, n_cy, od_word);
         if (rc) return rc;
         if ((rc = skip_k(ctx, pe_coarse))) return rc;
-        auto bk = fmt == RT_FORMAT_I32X4 ? trace_bin_kernel<RT_FORMAT_I32X4>
-                  : fmt == RT_FORMAT_HIT ? trace_bin_kernel<RT_FORMAT_HIT>
-                                         : trace_bin_kernel<RT_FORMAT_RGBA8>;
+        auto bk = RT_BY_FMT(trace_bin_kernel);
         ctx->last_kernel = RT_KERNEL_TRACE_BIN;
         rc = launch_k(bk, dim3((unsigned)(n_cx * kTiles), (unsigned)n_cy), dim3(64), stream,
                         kernel_events(ctx, pe_trace, true, true), n_chunks, width, row_begin,
@@ -2897,27 +2894,13 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
     }
 #if RT_DIAG
     // diagnostics build: the trace-kernel ablations (rt_debug_set_trace_mode)
-    auto kern = fmt == RT_FORMAT_I32X4
-                    ? (ctx->trace_mode == 1   ? trace3_kernel<1, RT_FORMAT_I32X4>
-                       : ctx->trace_mode == 2 ? trace3_kernel<2, RT_FORMAT_I32X4>
-                       : ctx->trace_mode == 3 ? trace3_kernel<3, RT_FORMAT_I32X4>
-                       : ctx->trace_mode == 4 ? trace3_kernel<4, RT_FORMAT_I32X4>
-                                              : trace3_kernel<0, RT_FORMAT_I32X4>)
-                : fmt == RT_FORMAT_HIT
-                    ? (ctx->trace_mode == 1   ? trace3_hit_kernel<1>
-                       : ctx->trace_mode == 2 ? trace3_hit_kernel<2>
-                       : ctx->trace_mode == 3 ? trace3_hit_kernel<3>
-                       : ctx->trace_mode == 4 ? trace3_hit_kernel<4>
-                                              : trace3_hit_kernel<0>)
-                    : (ctx->trace_mode == 1   ? trace3_kernel<1, RT_FORMAT_RGBA8>
-                       : ctx->trace_mode == 2 ? trace3_kernel<2, RT_FORMAT_RGBA8>
-                       : ctx->trace_mode == 3 ? trace3_kernel<3, RT_FORMAT_RGBA8>
-                       : ctx->trace_mode == 4 ? trace3_kernel<4, RT_FORMAT_RGBA8>
-                                              : trace3_kernel<0, RT_FORMAT_RGBA8>);
+    auto kern = ctx->trace_mode == 1   ? RT_TRACE3_BY_FMT(1)
+                : ctx->trace_mode == 2 ? RT_TRACE3_BY_FMT(2)
+                : ctx->trace_mode == 3 ? RT_TRACE3_BY_FMT(3)
+                : ctx->trace_mode == 4 ? RT_TRACE3_BY_FMT(4)
+                                       : RT_TRACE3_BY_FMT(0);
 #else
-    auto kern = fmt == RT_FORMAT_I32X4 ? trace3_kernel<0, RT_FORMAT_I32X4>
-                : fmt == RT_FORMAT_HIT ? trace3_hit_kernel<0>
-                                       : trace3_kernel<0, RT_FORMAT_RGBA8>;
+    auto kern = RT_TRACE3_BY_FMT(0);
 #endif
     const dim3 trace_grid((unsigned)(n_cx * kTiles), (unsigned)n_cy);
     // Small frames: several waves per wave tile (trace3_split_kernel) while
@@ -2931,9 +2914,7 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
                                                    : 1;
     if (split > 1 && ctx->trace_mode == 0) {
         ctx->last_kernel = RT_KERNEL_TRACE_SPLIT;
-        auto sk = fmt == RT_FORMAT_I32X4 ? trace3_split_kernel<RT_FORMAT_I32X4>
-                  : fmt == RT_FORMAT_HIT ? trace3_split_kernel<RT_FORMAT_HIT>
-                                         : trace3_split_kernel<RT_FORMAT_RGBA8>;
+        auto sk = RT_BY_FMT(trace3_split_kernel);
         rc = launch_k(sk, trace_grid, dim3(64 * split), stream,
                         kernel_events(ctx, pe_trace, true, true), sd, (const TriRec*)tri,
                         (const SphRec*)sph, (const float4*)colours, (const int*)counts,

@@ -1,7 +1,10 @@
 """The C-ABI boundary (include/rt_hip.h): library loads, exports every
 declared symbol, and validates arguments without a GPU."""
 import ctypes
+import os
 import re
+import shutil
+import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -38,13 +41,31 @@ def test_library_exports_every_declared_symbol(pkg):
 def test_default_build_has_no_diagnostics(pkg):
     """The shipped library (RT_DIAG=0) exports none of the diagnostics
     build's hooks (include/rt_hip_diag.h) and instantiates no ablation
-    variant of the trace kernel: only trace3_kernel<0, format>."""
+    variant of the trace kernel: only trace3_kernel<0, format>, once per
+    output format (int32x4 = 0, RGBA8 = 1, HIT = 3)."""
     lib = ctypes.CDLL(str(pkg.library_path()))
     diag = declared_functions(DIAG_HEADER)
     assert "rt_debug_set_trace_mode" in diag
     assert not [n for n in diag if hasattr(lib, n)]
     names = set(re.findall(rb"trace3_kernelILi(\d)ELi(\d)E", pkg.library_path().read_bytes()))
-    assert names == {(b"0", b"0"), (b"0", b"1")}, names
+    assert names == {(b"0", b"0"), (b"0", b"1"), (b"0", b"3")}, names
+
+
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+
+
+@pytest.mark.skipif(not Path(HIPCC).exists(), reason="needs hipcc")
+def test_removed_knob_stops_the_build():
+    """A -D of a compile-time experiment that was decided and removed
+    (rt_trace.inc's guard block) must not build the default unnoticed: the
+    preprocessor stops and points at DESIGN.md.  Preprocessing only: no
+    device, no code generation."""
+    src = REPO / "opencl-ray-tracer_amd" / "csrc" / "rt_device.hip"
+    r = subprocess.run([HIPCC, "-E", "--cuda-host-only", "-std=c++17", "-DRT_DIAG=0",
+                        "-DRT_WALK_BALLOT=1", "-I", str(REPO / "include"), "-o", os.devnull,
+                        str(src)], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0
+    assert "DESIGN.md" in r.stderr, r.stderr[-2000:]
 
 
 def test_abi_version(pkg):
