@@ -92,9 +92,9 @@ typedef struct rt_scene {
     const float* cube_vertices;
     const float* cube_colours;
     int32_t num_cubes;
-    /* float4[num_lights].  Carried for ABI completeness; the reference has no
-     * lighting model (its "shade" is a depth ramp, MainState.cpp:396-407), so
-     * lights never change the output. */
+    /* float4[num_lights]: xyz the position, w reserved.  Renders ignore
+     * lights (the reference has no lighting model, its "shade" is a depth
+     * ramp, MainState.cpp:396-407); rt_light_hits* read them. */
     const float* lights;
     int32_t num_lights;
 } rt_scene;
@@ -326,6 +326,61 @@ void rt_pack_rgba8(const int32_t* frame, int64_t n_pixels, uint32_t* out);
  * partly written. */
 int rt_shade_hits(const rt_hit* hits, int64_t n_pixels, const rt_scene* scene,
                   int32_t out_format, void* out);
+
+/* ---- deferred surfaces and diffuse lighting from a hit frame ----------- */
+/* No reference counterpart (the reference shades a depth ramp and nothing
+ * else).  Input is a band of an RT_FORMAT_HIT frame of implicit origins:
+ * hits[(row_end - row_begin) * width], row-major, pixel (x, row_begin + r)
+ * with origin ((float)x, (float)y, 0) and direction ray_dir.xyz.  The
+ * arithmetic is fp32 with one rounding per operation and is stated in
+ * DESIGN.md §3.1a; host and device results are bit-identical.
+ *
+ * One pixel of rt_hit_surfaces* (16 bytes): the unit normal turned against
+ * the ray and, for a cube, which of its twelve triangles was hit (the first
+ * in the reference's order whose fp64 test gives the frame's t).  Spheres
+ * and misses have triangle = -1; a miss, and a cube pixel whose t none of
+ * its triangles reproduces (a hit frame this library did not make), have
+ * n = 0. */
+typedef struct rt_surface {
+    float nx, ny, nz;
+    int32_t triangle;
+} rt_surface;
+
+/* Host functions, no GPU needed: `hits`, the arrays of `scene` and `out`
+ * are host pointers.  rt_light_hits writes rt_shade_hits' pixel with the
+ * depth ramp scaled by k = min(1, sum over scene->lights of the positive
+ * cosines between the normal and the direction to the light); with
+ * num_lights == 0, k = 1 and the frame is rt_shade_hits' frame, and so the
+ * trace's, bit for bit.  out_format is RT_FORMAT_I32X4 or RT_FORMAT_RGBA8.
+ * RT_ERR_INVALID_ARG: a NULL pointer, width < 1, row_begin < 0, row_end <=
+ * row_begin, width or row_end above 2^24, a negative count, an array
+ * missing for a non-zero count, another out_format, or an `object` outside
+ * [-1, num_cubes + num_spheres) (`out` may then be partly written). */
+int rt_hit_surfaces(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                    int32_t width, int32_t row_begin, int32_t row_end, rt_surface* out);
+int rt_light_hits(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                  int32_t width, int32_t row_begin, int32_t row_end, int32_t out_format,
+                  void* out);
+
+/* The same on the device, one kernel launch: `device_hits`, every pointer in
+ * `device_scene` and `device_out` are device pointers on the context's
+ * device (the rt_scene struct itself and ray_dir are read on the host
+ * during the call).  Asynchronous on `stream` (NULL = the context's stream),
+ * so a trace into a hit frame and its lighting can follow each other on one
+ * stream with no host synchronisation.  `device_hits` must be 8-byte
+ * aligned and `device_out` aligned to its pixel: 16 bytes for surfaces and
+ * I32X4, 4 for RGBA8; a misaligned pointer is RT_ERR_INVALID_ARG, as is
+ * everything the host functions check except the object ids: a kernel
+ * returns no status, so it range-checks `object` before any index and
+ * treats an id outside [-1, num_cubes + num_spheres) as -1 (no object:
+ * zero surface, k = 1 and the colour (0, 0, 0)).  RT_ERR_UNSUPPORTED for
+ * a band of 2^39 pixels or more (one launch's grid). */
+int rt_hit_surfaces_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
+                           const float ray_dir[4], int32_t width, int32_t row_begin,
+                           int32_t row_end, rt_surface* device_out, void* stream);
+int rt_light_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
+                         const float ray_dir[4], int32_t width, int32_t row_begin,
+                         int32_t row_end, int32_t out_format, void* device_out, void* stream);
 
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`

@@ -1,0 +1,203 @@
+/*
+ * rt_light_impl.h -- the per-pixel arithmetic of rt_hit_surfaces* and
+ * rt_light_hits* (DESIGN.md §3.1a), one text for the host functions
+ * (csrc/rt_light.cpp) and the kernel (csrc/rt_light.hip), and their shared
+ * argument check.  Internal: not installed, not part of the ABI.
+ *
+ * Every fp32 operation is written on its own and rounds once; both builds
+ * use -ffp-contract=off, the device's '/' and sqrtf are IEEE
+ * (-fhip-fp32-correctly-rounded-divide-sqrt).  Sums are parenthesised in the
+ * order DESIGN.md states.  NaN compares false everywhere.
+ */
+#ifndef RT_LIGHT_IMPL_H
+#define RT_LIGHT_IMPL_H
+
+#include <math.h>
+#include <stdint.h>
+
+#include "rt_hip.h"
+
+/* rt_light.hip defines this as `__host__ __device__ inline` before including */
+#ifndef RT_LIGHT_FN
+#define RT_LIGHT_FN inline
+#endif
+
+namespace rt_light {
+
+/* The common checks of the four entry points (0 or RT_ERR_INVALID_ARG):
+ * NULL pointers, width / rows (the pixel-coordinate limits of
+ * rt_args::check_args), counts, and arrays missing for a non-zero count,
+ * lights included.  csrc/rt_light.cpp. */
+int check(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32_t width,
+          int32_t row_begin, int32_t row_end, const void* out);
+
+constexpr double kEpsilon = 0.000001;  // MainState.cpp:15
+constexpr float kFar = 300000.0f;      // MainState.cpp:345
+
+// (int)f as x86-64 cvttss2si: truncation, NaN / out of range -> INT32_MIN.
+RT_LIGHT_FN int32_t cvt_i32(float f) {
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? static_cast<int32_t>(f) : INT32_MIN;
+}
+
+// The Texture packing (MainState.cpp:1026-1036).
+RT_LIGHT_FN uint32_t pack_rgba8(const int32_t p[4]) {
+    return static_cast<uint32_t>(static_cast<uint8_t>(p[0])) |
+           (static_cast<uint32_t>(static_cast<uint8_t>(p[1])) << 8) |
+           (static_cast<uint32_t>(static_cast<uint8_t>(p[2])) << 16) | 0xFF000000u;
+}
+
+// The reference's fp64 Moeller-Trumbore test (MainState.cpp:257-298), the
+// text of intersect_tri in the generic kernel (rt_trace.inc).
+RT_LIGHT_FN int intersect_tri(const double* orig, const double* dir, const double* v0,
+                              const double* v1, const double* v2, double* t) {
+    double e1[3], e2[3], tv[3], pv[3], qv[3];
+    e1[0] = v1[0] - v0[0]; e1[1] = v1[1] - v0[1]; e1[2] = v1[2] - v0[2];
+    e2[0] = v2[0] - v0[0]; e2[1] = v2[1] - v0[1]; e2[2] = v2[2] - v0[2];
+    pv[0] = dir[1] * e2[2] - dir[2] * e2[1];
+    pv[1] = dir[2] * e2[0] - dir[0] * e2[2];
+    pv[2] = dir[0] * e2[1] - dir[1] * e2[0];
+    const double det = e1[0] * pv[0] + e1[1] * pv[1] + e1[2] * pv[2];
+    if (det > -kEpsilon && det < kEpsilon) return 0;
+    const double inv_det = 1.0 / det;
+    tv[0] = orig[0] - v0[0]; tv[1] = orig[1] - v0[1]; tv[2] = orig[2] - v0[2];
+    const double u = (tv[0] * pv[0] + tv[1] * pv[1] + tv[2] * pv[2]) * inv_det;
+    if (u < 0.0 || u > 1.0) return 0;
+    qv[0] = tv[1] * e1[2] - tv[2] * e1[1];
+    qv[1] = tv[2] * e1[0] - tv[0] * e1[2];
+    qv[2] = tv[0] * e1[1] - tv[1] * e1[0];
+    const double v = (dir[0] * qv[0] + dir[1] * qv[1] + dir[2] * qv[2]) * inv_det;
+    if (v < 0.0 || u + v > 1.0) return 0;
+    *t = (e2[0] * qv[0] + e2[1] * qv[1] + e2[2] * qv[2]) * inv_det;
+    return 1;
+}
+
+struct Vec3 {
+    float x, y, z;
+};
+
+// m / |m|, |m| = sqrtf((x*x + y*y) + z*z), three divisions
+RT_LIGHT_FN Vec3 normalise(Vec3 m) {
+    const float len = sqrtf((m.x * m.x + m.y * m.y) + m.z * m.z);
+    return Vec3{m.x / len, m.y / len, m.z / len};
+}
+
+// n turned against the ray: negated where (n . d) > 0
+RT_LIGHT_FN Vec3 face(Vec3 n, Vec3 d) {
+    const float s = (n.x * d.x + n.y * d.y) + n.z * d.z;
+    if (s > 0.0f) return Vec3{-n.x, -n.y, -n.z};
+    return n;
+}
+
+// The hit point of pixel (ox, oy): o + t * d with o.z = 0.
+RT_LIGHT_FN Vec3 hit_point(float ox, float oy, Vec3 d, float t) {
+    return Vec3{ox + t * d.x, oy + t * d.y, 0.0f + t * d.z};
+}
+
+// Cube pixels: the first of the cube's twelve triangles (float4[36] at
+// `verts`) whose fp64 test hits with (float)t == the frame's t, and its
+// unit normal (unfaced).  No match: triangle -1, normal 0.
+RT_LIGHT_FN rt_surface cube_surface(const float* verts, float ox, float oy, Vec3 d, float t) {
+    const double o[3] = {ox, oy, 0.0};
+    const double dir[3] = {d.x, d.y, d.z};
+    int tri = -1;
+    for (int k = 0; k < 12; ++k) {
+        const float* a = verts + 12 * k;
+        const float* b = a + 4;
+        const float* c = a + 8;
+        const double v0[3] = {a[0], a[1], a[2]}, v1[3] = {b[0], b[1], b[2]},
+                     v2[3] = {c[0], c[1], c[2]};
+        double td;
+        if (intersect_tri(o, dir, v0, v1, v2, &td) == 1 && static_cast<float>(td) == t) {
+            tri = k;
+            break;
+        }
+    }
+    if (tri < 0) return rt_surface{0.0f, 0.0f, 0.0f, -1};
+    // (after the loop: on the device the lanes of a wave leave it at different
+    // k, and the normal is then computed once, not once per distinct k)
+    const float* a = verts + 12 * tri;
+    const float* b = a + 4;
+    const float* c = a + 8;
+    const Vec3 e1{b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    const Vec3 e2{c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+    const Vec3 n = normalise(Vec3{e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z,
+                                  e1.x * e2.y - e1.y * e2.x});
+    return rt_surface{n.x, n.y, n.z, tri};
+}
+
+// The float4[36] of cube `obj` (NULL when `obj` is no cube).
+RT_LIGHT_FN const float* cube_verts(const rt_scene& s, int32_t obj) {
+    return obj >= 0 && obj < s.num_cubes ? s.cube_vertices + 144 * static_cast<int64_t>(obj)
+                                         : nullptr;
+}
+
+// The surface of one pixel.  `obj` is already range-checked: -1 (nothing
+// hit) or a colour slot of `s`; `verts` = cube_verts(s, obj).  `p` is the
+// pixel's hit point.
+RT_LIGHT_FN rt_surface surface(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                               float oy, Vec3 d, float t, Vec3 p) {
+    if (obj < 0) return rt_surface{0.0f, 0.0f, 0.0f, -1};
+    rt_surface r;
+    if (obj < s.num_cubes) {
+        r = cube_surface(verts, ox, oy, d, t);
+    } else {
+        const float* c = s.sphere_origins + 4 * static_cast<int64_t>(obj - s.num_cubes);
+        const Vec3 n = normalise(Vec3{p.x - c[0], p.y - c[1], p.z - c[2]});
+        r = rt_surface{n.x, n.y, n.z, -1};
+    }
+    const Vec3 n = face(Vec3{r.nx, r.ny, r.nz}, d);
+    return rt_surface{n.x, n.y, n.z, r.triangle};
+}
+
+// The lighting factor of a hit pixel with at least one light: the clamped
+// sum of the positive cosines between n and the directions to the lights
+// (float4 each, w ignored).
+RT_LIGHT_FN float light_factor(Vec3 n, Vec3 p, const float* lights, int32_t num_lights) {
+    float k = 0.0f;
+    for (int32_t i = 0; i < num_lights; ++i) {
+        const float* l = lights + 4 * static_cast<int64_t>(i);
+        const Vec3 L{l[0] - p.x, l[1] - p.y, l[2] - p.z};
+        const float ll = sqrtf((L.x * L.x + L.y * L.y) + L.z * L.z);
+        const float c = ((n.x * L.x + n.y * L.y) + n.z * L.z) / ll;
+        if (c > 0.0f) k = k + c;
+    }
+    if (k > 1.0f) k = 1.0f;
+    return k;
+}
+
+// rt_shade_hits' pixel (MainState.cpp:396-407) with the ramp scaled by k.
+RT_LIGHT_FN void shade_lit(float t, float k, Vec3 colour, int32_t out[4]) {
+    out[0] = out[1] = out[2] = 0;
+    out[3] = 255;
+    if (t == kFar) return;
+    const float normalised = (t - 0.0f) / (180.0f - 0.0f);
+    const float scalar = 255.0f - (normalised * 255.0f);
+    const float lit = scalar * k;
+    out[0] = cvt_i32(lit * colour.x);
+    out[1] = cvt_i32(lit * colour.y);
+    out[2] = cvt_i32(lit * colour.z);
+}
+
+// One lit pixel (int32x4).  `obj` and `verts` as for surface().
+RT_LIGHT_FN void lit_pixel(const rt_scene& s, int32_t obj, const float* verts, float ox, float oy,
+                           Vec3 d, float t, int32_t out[4]) {
+    // closestColour starts as (0, 0, 0, 255) (MainState.cpp:344)
+    Vec3 colour{0.0f, 0.0f, 0.0f};
+    if (obj >= 0) {
+        const float* c = obj < s.num_cubes
+                             ? s.cube_colours + 4 * static_cast<int64_t>(obj)
+                             : s.sphere_colours + 4 * static_cast<int64_t>(obj - s.num_cubes);
+        colour = Vec3{c[0], c[1], c[2]};
+    }
+    float k = 1.0f;
+    if (s.num_lights > 0 && obj >= 0) {
+        const Vec3 p = hit_point(ox, oy, d, t);
+        const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
+        k = light_factor(Vec3{n.nx, n.ny, n.nz}, p, s.lights, s.num_lights);
+    }
+    shade_lit(t, k, colour, out);
+}
+
+}  // namespace rt_light
+
+#endif /* RT_LIGHT_IMPL_H */

@@ -26,7 +26,7 @@ __all__ = [
     "library", "library_path", "primary_ray_dir", "pack_rgba8", "cube_packed",
     "deg_to_rad", "encode_png", "EXPORTED_SYMBOLS", "CUBE_OP_DTYPE", "cube_ops", "render_multi",
     "debug_glibc_sincosf", "host_register", "host_unregister", "HIT_DTYPE", "HIT_MISS_T",
-    "shade_hits",
+    "shade_hits", "SURFACE_DTYPE", "hit_surfaces", "light_hits",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -41,6 +41,9 @@ _FORMATS = {"i32x4": RT_FORMAT_I32X4, "rgba8": RT_FORMAT_RGBA8, "hit": RT_FORMAT
 # (HIT_MISS_T, -1); object is the colour slot (cube c: c, sphere i: num_cubes + i).
 HIT_DTYPE = np.dtype([("t", "<f4"), ("object", "<i4")])
 HIT_MISS_T = np.float32(300000.0)
+# rt_surface (include/rt_hip.h): one pixel of hit_surfaces: the unit normal
+# turned against the ray and the cube triangle hit (-1: sphere or miss).
+SURFACE_DTYPE = np.dtype([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("triangle", "<i4")])
 _PATHS = {"auto": RT_PATH_AUTO, "binned": RT_PATH_BINNED, "generic": RT_PATH_GENERIC}
 
 # Every symbol include/rt_hip.h declares (tests check the .so exports them).
@@ -52,7 +55,8 @@ EXPORTED_SYMBOLS = (
     "rt_pack_rgba8", "rt_abi_version", "rt_cube_build_device", "rt_scene_synthetic_device",
     "rt_render_multi", "rt_shared_alloc", "rt_shared_open", "rt_shared_close", "rt_shared_free",
     "rt_host_register", "rt_host_unregister", "rt_reserve", "rt_last_kernel", "rt_fnv1a64",
-    "rt_shade_hits",
+    "rt_shade_hits", "rt_hit_surfaces", "rt_light_hits", "rt_hit_surfaces_device",
+    "rt_light_hits_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -158,6 +162,13 @@ def library() -> ctypes.CDLL:
         "rt_abi_version": (ctypes.c_int, []),
         "rt_fnv1a64": (ctypes.c_uint64, [vp, ctypes.c_int64, ctypes.c_uint64]),
         "rt_shade_hits": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), i32, vp]),
+        "rt_hit_surfaces": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32, vp]),
+        "rt_light_hits": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32, i32,
+                                         vp]),
+        "rt_hit_surfaces_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32, i32,
+                                                  i32, vp, vp]),
+        "rt_light_hits_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32, i32,
+                                                i32, i32, vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -351,7 +362,8 @@ class Scene:
     def synthetic(cls, width: int, height: int, n_spheres: int, n_cubes: int,
                   seed: int = 7, k: float = 1.0, n_lights: int = 0) -> "Scene":
         """SURVEY.md §8d synthetic N-sphere/M-cube scene; lights are carried
-        (the reference has no lighting model, so they never change pixels)."""
+        (the reference has no lighting model: renders ignore them, light_hits
+        reads them)."""
         so = np.zeros((n_spheres, 4), np.float32)
         sr = np.zeros(n_spheres, np.float32)
         sc = np.zeros((n_spheres, 4), np.float32)
@@ -415,6 +427,57 @@ def shade_hits(hits: np.ndarray, scene: Scene, fmt: str = "i32x4") -> np.ndarray
     _check(library().rt_shade_hits(_ptr(hits), hits.size, ctypes.byref(sc), _FORMATS[fmt],
                                    _ptr(out)), "rt_shade_hits")
     return out
+
+
+def _hit_band(hits: np.ndarray, rows: Optional[Tuple[int, int]]):
+    """A 2-D hit frame (rows x width) and the rows of the frame it holds."""
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype != HIT_DTYPE or hits.ndim != 2:
+        raise ValueError(f"hits must be a 2-D HIT_DTYPE array, got {hits.dtype} {hits.shape}")
+    rb, re = rows if rows is not None else (0, hits.shape[0])
+    if re - rb != hits.shape[0]:
+        raise ValueError(f"rows {rb}:{re} do not match the {hits.shape[0]} rows of hits")
+    return hits, rb, re
+
+
+def hit_surfaces(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
+                 ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_hit_surfaces: per pixel of a "hit" frame (rows x width HIT_DTYPE;
+    `rows` = the band of the frame it holds, default from row 0) the unit
+    normal turned against the ray and the cube triangle that was hit, as a
+    SURFACE_DTYPE array of the same shape.  On the host."""
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(hits.shape, SURFACE_DTYPE)
+    sc = scene.as_c()
+    _check(library().rt_hit_surfaces(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
+                                     _ptr(out)), "rt_hit_surfaces")
+    return out
+
+
+def light_hits(hits: np.ndarray, scene: Scene, fmt: str = "i32x4",
+               rows: Optional[Tuple[int, int]] = None,
+               ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_light_hits: shade_hits with the depth ramp scaled by the diffuse
+    term of `scene.lights` (see include/rt_hip.h); without lights it is
+    shade_hits' frame bit for bit.  On the host."""
+    if fmt not in ("i32x4", "rgba8"):
+        raise ValueError("light_hits gives an i32x4 or an rgba8 frame")
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
+    sc = scene.as_c()
+    _check(library().rt_light_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
+                                   _FORMATS[fmt], _ptr(out)), "rt_light_hits")
+    return out
+
+
+def _device_scene(device_scene: dict) -> _Scene:
+    """rt_scene of device addresses, lights included (hit post-passes)."""
+    g = device_scene.get
+    return _Scene(g("sphere_origins"), g("sphere_radius"), g("sphere_colours"),
+                  int(g("num_spheres", 0)), g("cube_vertices"), g("cube_colours"),
+                  int(g("num_cubes", 0)), g("lights"), int(g("num_lights", 0)))
 
 
 def host_register(buf: np.ndarray) -> None:
@@ -499,6 +562,37 @@ class RayTracer:
                                           origins_ptr or None, width, height, rows[0], rows[1],
                                           _FORMATS[fmt], _PATHS[path], out_ptr, stream or None),
                "rt_render_device")
+
+    def hit_surfaces_device(self, hits_ptr: int, device_scene: dict, width: int,
+                            rows: Tuple[int, int], out_ptr: int,
+                            ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
+        """rt_hit_surfaces_device: rows [rows[0], rows[1]) of a device hit
+        frame at `hits_ptr` to rt_surface records at `out_ptr` (16-byte
+        aligned).  Asynchronous on `stream`.  `device_scene` as for
+        render_device."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_hit_surfaces_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
+                                                _ptr(d), width, rows[0], rows[1],
+                                                out_ptr or None, stream or None),
+               "rt_hit_surfaces_device")
+
+    def light_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
+                          rows: Tuple[int, int], out_ptr: int,
+                          ray_dir: Optional[np.ndarray] = None, stream: int = 0,
+                          fmt: str = "i32x4") -> None:
+        """rt_light_hits_device: a device hit frame to a lit "i32x4" or "rgba8"
+        frame at `out_ptr`, with the lights of `device_scene` (optional keys
+        "lights": device address of float4[num_lights], "num_lights").
+        Asynchronous on `stream`."""
+        if fmt not in ("i32x4", "rgba8"):
+            raise ValueError("light_hits_device gives an i32x4 or an rgba8 frame")
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_light_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
+                                              _ptr(d), width, rows[0], rows[1], _FORMATS[fmt],
+                                              out_ptr or None, stream or None),
+               "rt_light_hits_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,

@@ -1,0 +1,146 @@
+"""Surfaces and diffuse lighting of a hit frame -- TEST INFRASTRUCTURE ONLY.
+
+A numpy restatement of DESIGN.md §3.1a for rt_hit_surfaces / rt_light_hits.
+Which of a cube's twelve triangles gave a pixel its t is found with the
+oracle's own fp64 `tri_t_grid`, triangle by triangle in the reference's
+order: no intersection arithmetic is restated.  Everything else is
+elementwise `np.float32` arithmetic, one ufunc per written operation (numpy
+never contracts), in the written order.
+"""
+import numpy as np
+
+from hit_ref import K_FAR, REF_DIR, hit_ref
+
+F32 = np.float32
+INT_MIN = -(1 << 31)
+_CACHE = {}
+
+
+def surface_dtype():
+    return np.dtype([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("triangle", "<i4")])
+
+
+def with_lights(scene, lights):
+    """`scene` with the given float4 lights (xyz position, w reserved)."""
+    return type(scene)(scene.sphere_origins, scene.sphere_radius, scene.sphere_colours,
+                       scene.cube_vertices, scene.cube_colours,
+                       np.asarray(lights, F32).reshape(-1, 4))
+
+
+def cached_hits(oracle, key, scene, w, h, rows=None, ray_dir=REF_DIR):
+    """hit_ref, computed once per key and read-only."""
+    k = ("hits", key, w, h, rows, tuple(ray_dir))
+    if k not in _CACHE:
+        r = hit_ref(oracle, scene, w, h, rows=rows, ray_dir=ray_dir)
+        r.setflags(write=False)
+        _CACHE[k] = r
+    return _CACHE[k]
+
+
+def _unit(mx, my, mz):
+    length = np.sqrt((mx * mx + my * my) + mz * mz)
+    return mx / length, my / length, mz / length
+
+
+def hit_points(hits, row_begin, ray_dir):
+    """p = (x + t*d.x, y + t*d.y, 0 + t*d.z) per pixel, three (rows x w) arrays."""
+    n, w = hits.shape
+    d = np.asarray(ray_dir, F32)
+    x = np.broadcast_to(np.arange(w, dtype=F32)[None, :], (n, w))
+    y = np.broadcast_to((row_begin + np.arange(n)).astype(F32)[:, None], (n, w))
+    t = hits["t"]
+    with np.errstate(all="ignore"):
+        return x + t * d[0], y + t * d[1], F32(0.0) + t * d[2]
+
+
+def surfaces_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR):
+    """(rows x w) surface records of a hit frame band starting at row_begin."""
+    n, w = hits.shape
+    d = np.ascontiguousarray(ray_dir, F32)
+    t, obj = hits["t"], hits["object"]
+    nc = scene.num_cubes
+    nx, ny, nz = (np.zeros((n, w), F32) for _ in range(3))
+    tri = np.full((n, w), -1, np.int32)
+    px, py, pz = hit_points(hits, row_begin, d)
+    cubes = np.ascontiguousarray(scene.cube_vertices, F32).reshape(-1, 36, 4)
+    with np.errstate(all="ignore"):
+        for c in np.unique(obj[(obj >= 0) & (obj < nc)]):
+            todo = obj == c
+            for k in range(12):
+                v0, v1, v2 = cubes[c, 3 * k, :3], cubes[c, 3 * k + 1, :3], cubes[c, 3 * k + 2, :3]
+                td = oracle.tri_t_grid(cubes[c, 3 * k], cubes[c, 3 * k + 1], cubes[c, 3 * k + 2],
+                                       d, 0, row_begin, w, n)
+                match = todo & ~np.isnan(td) & (td.astype(F32) == t)
+                if not match.any():
+                    continue
+                e1, e2 = v1 - v0, v2 - v0
+                ux, uy, uz = _unit(e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
+                                   e1[0] * e2[1] - e1[1] * e2[0])
+                nx[match], ny[match], nz[match], tri[match] = ux, uy, uz, k
+                todo = todo & ~match
+        sph = obj >= nc
+        if sph.any():
+            centre = np.ascontiguousarray(scene.sphere_origins, F32).reshape(-1, 4)[obj[sph] - nc]
+            nx[sph], ny[sph], nz[sph] = _unit(px[sph] - centre[:, 0], py[sph] - centre[:, 1],
+                                              pz[sph] - centre[:, 2])
+        s = (nx * d[0] + ny * d[1]) + nz * d[2]
+        flip = s > 0
+        nx[flip], ny[flip], nz[flip] = -nx[flip], -ny[flip], -nz[flip]
+    out = np.empty((n, w), surface_dtype())
+    out["nx"], out["ny"], out["nz"], out["triangle"] = nx, ny, nz, tri
+    return out
+
+
+def light_factor_ref(scene, hits, surf, row_begin=0, ray_dir=REF_DIR):
+    """k per pixel: 1 without lights or without an object, else the clamped
+    sum of the positive cosines."""
+    n, w = hits.shape
+    lights = np.ascontiguousarray(scene.lights, F32).reshape(-1, 4)
+    k = np.ones((n, w), F32)
+    if len(lights) == 0:
+        return k
+    px, py, pz = hit_points(hits, row_begin, ray_dir)
+    acc = np.zeros((n, w), F32)
+    with np.errstate(all="ignore"):
+        for l in lights:
+            lx, ly, lz = l[0] - px, l[1] - py, l[2] - pz
+            ll = np.sqrt((lx * lx + ly * ly) + lz * lz)
+            c = ((surf["nx"] * lx + surf["ny"] * ly) + surf["nz"] * lz) / ll
+            acc = np.where(c > 0, acc + c, acc)
+        acc = np.where(acc > 1, F32(1.0), acc)
+    return np.where(hits["object"] == -1, F32(1.0), acc).astype(F32)
+
+
+def x86_int(v):
+    """(int)v as cvttss2si: NaN and out-of-range values give INT32_MIN."""
+    with np.errstate(invalid="ignore"):
+        ok = (v >= F32(-2147483648.0)) & (v < F32(2147483648.0))
+        return np.where(ok, np.where(ok, v, F32(0.0)).astype(np.int64), INT_MIN).astype(np.int32)
+
+
+def lit_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR, surf=None):
+    """The int32x4 frame of rt_light_hits (pack with oracle.pack_rgba8)."""
+    if surf is None:
+        surf = surfaces_ref(oracle, scene, hits, row_begin, ray_dir)
+    k = light_factor_ref(scene, hits, surf, row_begin, ray_dir)
+    t, obj = hits["t"], hits["object"]
+    table = np.concatenate([np.ascontiguousarray(scene.cube_colours, F32).reshape(-1, 4),
+                            np.ascontiguousarray(scene.sphere_colours, F32).reshape(-1, 4),
+                            np.array([[0, 0, 0, 255]], F32)])  # [-1]: no object
+    colour = table[obj]
+    out = np.zeros(hits.shape + (4,), np.int32)
+    out[..., 3] = 255
+    with np.errstate(all="ignore"):
+        normalised = (t - F32(0.0)) / (F32(180.0) - F32(0.0))
+        scalar = F32(255.0) - (normalised * F32(255.0))
+        lit = scalar * k
+        for ch in range(3):
+            out[..., ch] = x86_int(lit * colour[..., ch])
+    out[t == K_FAR] = (0, 0, 0, 255)
+    return out
+
+
+def words(a):
+    """Any 4-byte-element array or record array as raw uint32 words."""
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32).reshape(a.shape + (-1,)) if a.dtype.names else a.view(np.uint32)

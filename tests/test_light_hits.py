@@ -1,0 +1,328 @@
+"""rt_hit_surfaces / rt_light_hits without a GPU: the host functions against
+the numpy restatement (tests/light_ref.py), the zero-lights invariant against
+`shade_hits` and the oracle, exact cases, and the argument contract.
+
+Every comparison is on raw 32-bit words: the arithmetic is fully specified
+(DESIGN.md §3.1a), so there are no tolerances.
+"""
+import ctypes
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import light_ref as lr
+from hit_ref import K_FAR, REF_DIR, distinct_colours, hit_ref
+from test_gpu_numeric_edges import H, W, base_scene
+
+REPO = Path(__file__).resolve().parents[1]
+F32 = np.float32
+INT_MIN = -(1 << 31)
+UP_DIR = (0.0, 0.0, 1.0, 0.0)
+ONE_LIGHT = [(48, 40, 200, 1)]
+THREE_LIGHTS = ONE_LIGHT + [(0, 0, 50, 1), (120, 90, -20, 1)]
+# (key, w, h, rows, ray_dir): the frames of the base scene
+FRAMES = [("96x80", W, H, None, REF_DIR), ("83x45_rows_7_38", 83, 45, (7, 38), REF_DIR),
+          ("96x80_dir_0_0_1_0", W, H, None, UP_DIR)]
+FRAME_IDS = [f[0] for f in FRAMES]
+
+
+def base(pkg):
+    return distinct_colours(base_scene(pkg))
+
+
+def eq(got, want):
+    """'' or a description of the first differing pixel (raw words)."""
+    a, b = lr.words(got), lr.words(want)
+    if a.shape != b.shape:
+        return f"shape {a.shape} vs {b.shape}"
+    bad = (a != b).reshape(got.shape[:2] + (-1,)).any(-1)
+    if not bad.any():
+        return ""
+    ys, xs = np.nonzero(bad)
+    return (f"{int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): "
+            f"{got[ys[0], xs[0]]} vs {want[ys[0], xs[0]]}")
+
+
+def classes(scene, hits):
+    obj = hits["object"]
+    return (obj >= 0) & (obj < scene.num_cubes), obj >= scene.num_cubes, obj == -1
+
+
+# --- 0. the restatement is not vacuous --------------------------------------
+@pytest.mark.parametrize("key,w,h,rows,d", FRAMES, ids=FRAME_IDS)
+def test_light_ref_covers_every_class(pkg, oracle, key, w, h, rows, d):
+    scene = base(pkg)
+    assert scene.num_spheres == 40 and scene.num_cubes == 10
+    hits = lr.cached_hits(oracle, "base", scene, w, h, rows, d)
+    surf = lr.surfaces_ref(oracle, scene, hits, rows[0] if rows else 0, d)
+    cube, sphere, miss = classes(scene, hits)
+    assert cube.sum() > 0 and (surf["triangle"][cube] >= 0).all()  # every cube pixel resolves
+    assert (surf["triangle"][~cube] == -1).all()
+    if d == REF_DIR:
+        assert sphere.sum() > 0 and miss.sum() > 0
+    for f in ("nx", "ny", "nz"):
+        assert not np.isnan(surf[f]).any()
+    if key == "96x80":
+        assert set(np.unique(surf["triangle"][cube]).tolist()) == set(range(12))
+
+
+def test_light_ref_factor_spans_its_range(pkg, oracle):
+    scene = base(pkg)
+    hits = lr.cached_hits(oracle, "base", scene, W, H)
+    surf = lr.surfaces_ref(oracle, scene, hits)
+    hit = hits["object"] >= 0
+    k1 = lr.light_factor_ref(lr.with_lights(scene, ONE_LIGHT), hits, surf)
+    assert ((k1 > 0) & (k1 < 1) & hit).sum() > 100 and ((k1 == 0) & hit).sum() > 0
+    k3 = lr.light_factor_ref(lr.with_lights(scene, THREE_LIGHTS), hits, surf)
+    assert ((k3 == 1) & hit).sum() > 100 and ((k3 > 0) & (k3 < 1) & hit).sum() > 100
+    assert (k1[~hit] == 1).all() and (k3[~hit] == 1).all()
+
+
+# --- 1. surfaces --------------------------------------------------------------
+@pytest.mark.parametrize("key,w,h,rows,d", FRAMES, ids=FRAME_IDS)
+def test_hit_surfaces_equal_the_restatement(pkg, oracle, key, w, h, rows, d):
+    scene = base(pkg)
+    hits = lr.cached_hits(oracle, "base", scene, w, h, rows, d)
+    want = lr.surfaces_ref(oracle, scene, hits, rows[0] if rows else 0, d)
+    got = pkg.hit_surfaces(hits, scene, rows=rows, ray_dir=d)
+    assert got.dtype == pkg.SURFACE_DTYPE and got.shape == hits.shape
+    assert not eq(got, want), eq(got, want)
+
+
+# --- 2. zero lights: the reference's frame ------------------------------------
+def _one_sphere(pkg, origin, radius, colour):
+    return pkg.Scene(np.array([origin], F32), np.array([radius], F32), np.array([colour], F32))
+
+
+def _one_cube(pkg, ops, colour):
+    return pkg.Scene(cube_vertices=pkg.cube_packed(ops).reshape(1, 36, 4),
+                     cube_colours=np.array([colour], F32))
+
+
+MINUS_INF_DIR = (0.0, 0.0, -1e-4, -1.0)
+
+
+def edge_scenes(pkg):
+    """(key, scene, w, h, ray_dir): the base scene and the numeric edges of
+    the shade (tests/test_hit_format.py): t = -inf, a channel past int32, a
+    NaN colour."""
+    return [
+        ("base", base(pkg), W, H, REF_DIR),
+        ("minus_inf", _one_cube(pkg, [("scale", 20, 16, 1), ("translate", 16, 12, 3e38)],
+                                (1, 0.5, 0.0, 255)), 32, 24, MINUS_INF_DIR),
+        ("past_int32", _one_sphere(pkg, (16, 12, -10, 1), 2e9, (1.0, 0.25, -0.25, 255)), 32, 24,
+         REF_DIR),
+        ("nan_colour", _one_sphere(pkg, (16, 12, -50, 1), 9, (np.nan, 0.5, 1.0, 255)), 32, 24,
+         REF_DIR),
+    ]
+
+
+@pytest.mark.parametrize("i", range(4), ids=["base", "minus_inf", "past_int32", "nan_colour"])
+def test_zero_lights_is_the_reference_frame(pkg, oracle, i):
+    key, scene, w, h, d = edge_scenes(pkg)[i]
+    assert len(scene.lights) == 0
+    hits = lr.cached_hits(oracle, key, scene, w, h, None, d)
+    assert (hits["object"] >= 0).sum() > 50
+    want = oracle.trace(scene, w, h, ray_dir=np.asarray(d, F32))
+    if key == "minus_inf":
+        assert np.isneginf(hits["t"]).sum() > 50
+    if key != "base":
+        assert (want[..., :3] == INT_MIN).any()
+    for fmt, ref in (("i32x4", want), ("rgba8", oracle.pack_rgba8(want))):
+        got = pkg.light_hits(hits, scene, fmt, ray_dir=d)
+        assert got.dtype == ref.dtype and not eq(got, ref), f"{key} {fmt}: {eq(got, ref)}"
+        shaded = pkg.shade_hits(hits, scene, fmt)
+        assert not eq(got, shaded), f"{key} {fmt} vs shade_hits: {eq(got, shaded)}"
+
+
+# --- 3. lights ------------------------------------------------------------------
+@pytest.mark.parametrize("lights", [ONE_LIGHT, THREE_LIGHTS], ids=["one_light", "three_lights"])
+@pytest.mark.parametrize("key,w,h,rows,d", FRAMES[:2], ids=FRAME_IDS[:2])
+def test_light_hits_equal_the_restatement(pkg, oracle, key, w, h, rows, d, lights):
+    scene = lr.with_lights(base(pkg), lights)
+    hits = lr.cached_hits(oracle, "base", scene, w, h, rows, d)
+    want = lr.lit_ref(oracle, scene, hits, rows[0] if rows else 0, d)
+    unlit = pkg.shade_hits(hits, scene)
+    assert (want != unlit).any(-1).sum() > 100  # the lights do change pixels
+    for fmt, ref in (("i32x4", want), ("rgba8", oracle.pack_rgba8(want))):
+        got = pkg.light_hits(hits, scene, fmt, rows=rows, ray_dir=d)
+        assert not eq(got, ref), f"{fmt}: {eq(got, ref)}"
+
+
+def test_light_hits_minus_inf_with_lights(pkg, oracle):
+    """t = -inf: p is NaN, every cosine is NaN, k = 0; the ramp is +inf and
+    inf * 0 = NaN, so every channel of those pixels is INT32_MIN."""
+    key, scene, w, h, d = edge_scenes(pkg)[1]
+    scene = lr.with_lights(scene, THREE_LIGHTS)
+    hits = lr.cached_hits(oracle, key, scene, w, h, None, d)
+    neg = np.isneginf(hits["t"])
+    assert neg.sum() > 50
+    want = lr.lit_ref(oracle, scene, hits, 0, d)
+    assert (want[neg][:, :3] == INT_MIN).all()
+    for fmt, ref in (("i32x4", want), ("rgba8", oracle.pack_rgba8(want))):
+        got = pkg.light_hits(hits, scene, fmt, ray_dir=d)
+        assert not eq(got, ref), f"{fmt}: {eq(got, ref)}"
+
+
+# --- 4. exact cases -----------------------------------------------------------
+def test_axis_aligned_face_normal_and_triangles(pkg, oracle):
+    """A cube of scale (15, 15, 10) at z = -50: the face at z = -40 is seen
+    head on, its normal after facing is exactly (0, 0, 1), and the pixels
+    split between that face's two triangles."""
+    scene = _one_cube(pkg, [("scale", 15, 15, 10), ("translate", 32, 24, -50)], (1, 1, 1, 255))
+    hits = hit_ref(oracle, scene, 64, 48)
+    on = hits["object"] == 0
+    assert on.sum() > 500 and (hits["t"][on] == 40).all()
+    tri_z = scene.cube_vertices.reshape(12, 3, 4)[:, :, 2]
+    face = set(np.nonzero((tri_z == -40).all(1))[0].tolist())
+    assert len(face) == 2
+    surf = pkg.hit_surfaces(hits, scene)
+    assert set(np.unique(surf["triangle"][on]).tolist()) == face
+    assert (surf["nx"][on] == 0).all() and (surf["ny"][on] == 0).all()
+    assert (surf["nz"][on] == 1).all()
+    assert (lr.words(surf[~on]) == np.array([0, 0, 0, 0xFFFFFFFF], np.uint32)).all()
+
+
+def sphere_and_light(pkg, light_z):
+    s = _one_sphere(pkg, (32, 24, -50, 1), 20, (1.0, 0.5, 0.25, 255))
+    return lr.with_lights(s, [(32, 24, light_z, 1)])
+
+
+def test_light_on_the_axis_leaves_the_centre_pixel_unlit_value(pkg, oracle):
+    """Under the centre n = (0, 0, 1) and the light is straight ahead: k = 1."""
+    scene = sphere_and_light(pkg, 0)
+    hits = hit_ref(oracle, scene, 64, 48)
+    assert hits[24, 32]["object"] == 0 and hits[24, 32]["t"] == 30
+    lit, unlit = pkg.light_hits(hits, scene), pkg.shade_hits(hits, scene)
+    assert lit[24, 32].tolist() == unlit[24, 32].tolist() and lit[24, 32, 0] > 100
+    on = hits["object"] == 0
+    assert (lit[on][:, 0] < unlit[on][:, 0]).sum() > 500  # and dimmer towards the rim
+
+
+def test_light_behind_the_sphere_gives_black(pkg, oracle):
+    scene = sphere_and_light(pkg, -200)
+    hits = hit_ref(oracle, scene, 64, 48)
+    on = hits["object"] == 0
+    assert on.sum() > 500
+    lit = pkg.light_hits(hits, scene)
+    assert (lit[on] == (0, 0, 0, 255)).all()
+    assert (pkg.light_hits(hits, scene, "rgba8")[on] == 0xFF000000).all()
+
+
+# --- 5. contract ------------------------------------------------------------------
+def test_foreign_t_resolves_to_no_triangle(pkg, oracle):
+    scene = lr.with_lights(base(pkg), ONE_LIGHT)
+    hits = lr.cached_hits(oracle, "base", scene, W, H).copy()
+    cube, _, _ = classes(scene, hits)
+    y, x = (int(v[0]) for v in np.nonzero(cube))
+    before = pkg.hit_surfaces(hits, scene)[y, x]
+    assert before["triangle"] >= 0
+    for towards in (np.inf, -np.inf):
+        h = hits.copy()
+        h["t"][y, x] = np.nextafter(hits["t"][y, x], F32(towards))
+        s = pkg.hit_surfaces(h, scene)[y, x]
+        assert lr.words(s).reshape(-1).tolist() == [0, 0, 0, 0xFFFFFFFF]  # n = +0, triangle -1
+        for fmt, black in (("i32x4", [0, 0, 0, 255]), ("rgba8", 0xFF000000)):
+            assert np.array_equal(pkg.light_hits(h, scene, fmt)[y, x], black)
+
+
+def test_object_out_of_range_is_refused(pkg):
+    scene = lr.with_lights(base(pkg), ONE_LIGHT)
+    hits = np.zeros((2, 3), pkg.HIT_DTYPE)
+    hits["t"] = 50.0
+    hits["object"] = 49  # the last slot
+    assert pkg.light_hits(hits, scene).shape == (2, 3, 4)
+    assert pkg.hit_surfaces(hits, scene).shape == (2, 3)
+    for bad in (50, -2, 2**31 - 1, -2**31):
+        h = hits.copy()
+        h[1, 2]["object"] = bad
+        for call in (lambda: pkg.hit_surfaces(h, scene), lambda: pkg.light_hits(h, scene),
+                     lambda: pkg.light_hits(h, scene, "rgba8")):
+            with pytest.raises(pkg.RtError) as e:
+                call()
+            assert e.value.status == pkg.RT_ERR_INVALID_ARG
+
+
+def test_formats_widths_and_rows_are_refused(pkg):
+    scene = base(pkg)
+    hits = np.zeros((4, 5), pkg.HIT_DTYPE)
+    hits["t"], hits["object"] = K_FAR, -1
+    with pytest.raises(ValueError):
+        pkg.light_hits(hits, scene, "hit")
+    with pytest.raises(ValueError):
+        pkg.light_hits(hits, scene, rows=(0, 3))  # four rows of hits
+    with pytest.raises(ValueError):
+        pkg.hit_surfaces(hits.reshape(-1), scene)
+    lib, sc, d = pkg.library(), scene.as_c(), np.array(REF_DIR, F32)
+    out = np.zeros((4, 5, 4), np.int32)
+    hp, dp, op, bad = hits.ctypes.data, d.ctypes.data, out.ctypes.data, pkg.RT_ERR_INVALID_ARG
+
+    def light(width, rb, re, fmt=0, hits_p=hp, scene_p=ctypes.byref(sc), dir_p=dp, out_p=op):
+        return lib.rt_light_hits(hits_p, scene_p, dir_p, width, rb, re, fmt, out_p)
+
+    def surfaces(width, rb, re, hits_p=hp, scene_p=ctypes.byref(sc), dir_p=dp, out_p=op):
+        return lib.rt_hit_surfaces(hits_p, scene_p, dir_p, width, rb, re, out_p)
+
+    assert light(5, 0, 4) == 0 and light(5, 0, 4, 1) == 0 and surfaces(5, 0, 4) == 0
+    assert light(5, 1 << 20, (1 << 20) + 4) == 0
+    for fmt in (2, 3, 4, -1):
+        assert light(5, 0, 4, fmt) == bad
+    for fn in (light, surfaces):
+        for width, rb, re in ((0, 0, 4), (-1, 0, 4), ((1 << 24) + 1, 0, 1), (5, -1, 3), (5, 4, 4),
+                              (5, 4, 3), (5, 1 << 24, (1 << 24) + 1)):
+            assert fn(width, rb, re) == bad, (fn.__name__, width, rb, re)
+        for kw in ("hits_p", "scene_p", "dir_p", "out_p"):
+            assert fn(5, 0, 4, **{kw: None}) == bad, (fn.__name__, kw)
+    # counts: negative, or an array missing for a non-zero count
+    for fields in ({"num_lights": -1}, {"num_lights": 1, "lights": None}, {"num_cubes": -1},
+                   {"num_spheres": -1}, {"cube_vertices": None}, {"sphere_origins": None}):
+        c = scene.as_c()
+        for field, value in fields.items():
+            setattr(c, field, value)
+        assert light(5, 0, 4, scene_p=ctypes.byref(c)) == bad, fields
+        assert surfaces(5, 0, 4, scene_p=ctypes.byref(c)) == bad, fields
+
+
+def test_device_entries_refuse_a_null_context(pkg):
+    """Before any HIP call: this runs without a GPU."""
+    lib, sc, d = pkg.library(), base(pkg).as_c(), np.array(REF_DIR, F32)
+    buf = np.zeros(64, np.int32)
+    p = buf.ctypes.data
+    assert lib.rt_hit_surfaces_device(None, p, ctypes.byref(sc), d.ctypes.data, 2, 0, 2, p,
+                                      None) == pkg.RT_ERR_INVALID_ARG
+    for fmt in (0, 1):
+        assert lib.rt_light_hits_device(None, p, ctypes.byref(sc), d.ctypes.data, 2, 0, 2, fmt, p,
+                                        None) == pkg.RT_ERR_INVALID_ARG
+
+
+def test_python_mirror_names(pkg):
+    assert pkg.SURFACE_DTYPE == lr.surface_dtype() and pkg.SURFACE_DTYPE.itemsize == 16
+    for name in ("hit_surfaces", "light_hits", "SURFACE_DTYPE"):
+        assert name in pkg.__all__
+    for name in ("rt_hit_surfaces", "rt_light_hits", "rt_hit_surfaces_device",
+                 "rt_light_hits_device"):
+        assert name in pkg.EXPORTED_SYMBOLS
+    assert pkg.library().rt_abi_version() == 1
+
+
+# --- 6. under the sanitizers ------------------------------------------------------
+@pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
+def test_light_arguments_under_sanitizers(tmp_path):
+    """tests/light_args_check.cpp with csrc/rt_light.cpp (and the argument
+    checks it calls, csrc/rt_args.cpp) under AddressSanitizer +
+    UndefinedBehaviorSanitizer: exactly-sized heap arrays, empty scenes with
+    NULL arrays, a one-row band at a large row_begin."""
+    csrc = REPO / "opencl-ray-tracer_amd" / "csrc"
+    exe = tmp_path / "light_args_check"
+    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-std=c++17",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{REPO / 'include'}", "-o", str(exe),
+                    str(REPO / "tests" / "light_args_check.cpp"), str(csrc / "rt_light.cpp"),
+                    str(csrc / "rt_args.cpp"), "-lm"], check=True, capture_output=True, text=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "light args check ok" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
