@@ -25,7 +25,8 @@
 // The kernels and their host launch() are in rt_trace.inc, compiled here
 // twice: 16x16 wave tiles (namespace tile16) and 128x2 tiles (namespace
 // wide, frames of >= 512 MiB, whose stores drain faster from 2-KiB row
-// segments).
+// segments).  Which kernels a frame takes is decided by
+// rt_dispatch::choose() (rt_dispatch.h, host-only).
 // This file holds the context, the dispatcher and the C ABI.
 //
 // Build: -ffp-contract=off (and the pragma below): every operation rounds
@@ -44,6 +45,7 @@
 #include <vector>
 
 #include "rt_args.h"
+#include "rt_dispatch.h"
 #include "rt_hip.h"
 #include "rt_hip_debug.h"
 #include "rt_hip_diag.h"
@@ -61,87 +63,10 @@
 #error "RT_TIMELINE and RT_SKIP_DIAG are diagnostics: build with RT_DIAG=1"
 #endif
 
-#ifndef RT_BIN_MASKS
-#define RT_BIN_MASKS 1            // default of rt_debug_set_bin_masks
-#endif
-#ifndef RT_COARSE_CULL
-#define RT_COARSE_CULL 10  // default of rt_debug_set_coarse_cull: bins with >= 10 sphere candidates
-#endif
-#ifndef RT_COARSE_CULL_TRI
-#define RT_COARSE_CULL_TRI 4  // default of rt_debug_set_coarse_cull_tri: triangles join the cull
-                              // in bins whose tiles keep >= this many candidates on average
-#endif
-#ifndef RT_SMALL_FUSED
-#define RT_SMALL_FUSED 1  // default of rt_debug_set_small_fused
-#endif
-#ifndef RT_COARSE_CULL_OVERDRAW
-#define RT_COARSE_CULL_OVERDRAW 5  // default of rt_debug_set_coarse_cull_overdraw: ... in frames
-                                   // whose primitive boxes cover the frame >= 5 times
-#endif
-#ifndef RT_COARSE_CULL_TRI_RGBA8
-#define RT_COARSE_CULL_TRI_RGBA8 2  // the triangle threshold for Texture (RGBA8) renders
-#endif
-#ifndef RT_COARSE_CULL_OVERDRAW_RGBA8
-#define RT_COARSE_CULL_OVERDRAW_RGBA8 0  // the same gate for Texture (RGBA8) renders: every
-                                         // frame (its trace is bound by its tests, not by
-                                         // its stores)
-#endif
-// ... and for hit-buffer (RT_FORMAT_HIT) renders, measured on HIT frames of
-// config 3's scene at five object sizes: the triangle
-// threshold of 2 is 1.6-2 us per frame faster than 4 wherever the cull runs,
-// and the cull pays from a box overdraw of about 2 frames on (1.4: 41.5 us
-// without, 44.2 with; 2.8: 43.7 / 43.1; 4.3: 49.6 / 43.5)
-#ifndef RT_COARSE_CULL_TRI_HIT
-#define RT_COARSE_CULL_TRI_HIT 2
-#endif
-#ifndef RT_COARSE_CULL_OVERDRAW_HIT
-#define RT_COARSE_CULL_OVERDRAW_HIT 2
-#endif
-#ifndef RT_SPLIT4_TILES
-#define RT_SPLIT4_TILES 2048  // trace3_split_kernel with 4 waves per tile up to this many tiles
-#endif
-#ifndef RT_SPLIT2_TILES
-#define RT_SPLIT2_TILES 4096  // ... with 2 waves per tile up to this many (round 4: at
-                              // 8160, 1920x1080, flat; 4 waves win below 2048 tiles,
-                              // 2 up to 4096, one above)
-#endif
-#ifndef RT_COARSE_W8_BINS
-#define RT_COARSE_W8_BINS 256  // coarse3_kernel with 8 waves per bin in bands up to this many
-                               // bins (round 4: 80 and 240 bins 0.3-2.3 us faster than 4)
-#endif
-#ifndef RT_COARSE_W4_BINS
-#define RT_COARSE_W4_BINS 1024  // coarse3_kernel with 4 waves per bin in bands up to this many
-                                // bins (round 4: 4 waves fastest from 80 to 920 bins, one
-                                // at 4096 and up)
-#endif
-#ifndef RT_COARSE_W2_BINS
-#define RT_COARSE_W2_BINS 1024  // ... with 2 waves per bin up to this many (none by default)
-#endif
-#ifndef RT_TRACE_BIN_OD10
-#define RT_TRACE_BIN_OD10 40  // trace_bin_kernel (auto) for int32x4 frames below this box overdraw,
-                              // in tenths of a frame (round 5, one stream, config 3's scene scaled:
-                              // overdraw 0.08 / 0.3 / 0.7 / 1.4 / 2.8 / 4.3 / 6.1 frames, coarse path
-                              // 55.0 / 56.0 / 55.5 / 55.8 / 57.4 / 60.0 / 61.5 us per frame, no coarse
-                              // 51.3 / 51.3 / 49.6 / 49.8 / 53.9 / 60.9 / 69.2)
-#endif
-#ifndef RT_TRACE_BIN_OD10_RGBA8
-#define RT_TRACE_BIN_OD10_RGBA8 10  // ... for RGBA8 frames (same scenes: coarse path 37.5 / 39.3 /
-                                    // 40.2 / 42.0 / 44.5 / 46.7 / 47.9, no coarse 29.9 / 31.6 / 34.3 /
-                                    // 40.0 / 49.3 / 58.1 / 65.9; with 3 frames in flight at overdraw
-                                    // 0.08 / 1.4 / 2.8: coarse 18.3 / 27.5 / 32.5, no coarse 17.3 /
-                                    // 30.6 / 40.6, so 1 frame, not the one-stream crossover)
-#endif
+// (the dispatch policy's compile-time defaults: include/rt_dispatch.h)
 #ifndef RT_VERDICT_DIRECT
 #define RT_VERDICT_DIRECT 1  // the kernels write the overdraw verdict into the host word themselves
                              // (every binned launch, no copy; rt_ctx::od_verdict)
-#endif
-#ifndef RT_COARSE_CULL_TRI_BINS
-#define RT_COARSE_CULL_TRI_BINS 768  // triangles join the cull only in bands of at least this
-                                     // many coarse bins: fewer coarse waves run as one
-                                     // generation and cannot hide the cull's latency (round 4:
-                                     // 640x480 to 1920x1080 frames 1-27 us slower with it at
-                                     // box overdraw 5-20, 2560x1440 up to 16 us faster;
-                                     // DESIGN.md §3.5)
 #endif
 
 // ===========================================================================
@@ -185,41 +110,9 @@ struct rt_ctx {
     unsigned long long od_area = 0;  // the last such launch's area, 64-pixel units
     int trace_mode = 0;  // diagnostics ablation (RT_DIAG builds), see trace3_kernel
     int last_kernel = RT_KERNEL_NONE;  // the dominant kernel of the last launch (rt_last_kernel)
-    int tile_variant = 0;  // 0 = by frame size, 1 = 16x16 tiles, 2 = the wide (128x2) tiles
-    // coarse lists take 4 B x kListStride x (primitives + 16) per 64x64 bin; a frame whose
-    // lists would exceed this is rendered as internal row bands
-    int64_t list_budget = (int64_t)4 << 30;
-    bool bin_masks = RT_BIN_MASKS != 0;  // separable bin masks (false: coarse scans every box)
-    bool small_path = true;  // <= 64 x RT_SMALL_CHUNKS primitives: trace_small_kernel
-    // <= 64 x RT_FUSED_CHUNKS primitives on frames whose grid is resident at
-    // once: frame_small_kernel (1; 2 = on every frame size, tests; 0 = off)
-    int small_fused = RT_SMALL_FUSED;
-    // waves per wave tile in the binned trace: 0 = by frame size
-    // (trace3_split_kernel on small frames), 1 = one (trace3_kernel), 2 / 4
-    int trace_split = 0;
-    // waves per coarse bin: 0 = by band size, 1 / 2 / 4 / 8
-    int coarse_waves = 0;
-    // binned frames without the coarse kernel (trace_bin_kernel): 0 = auto
-    // (frames above the split sizes whose last binned frame had a box
-    // overdraw below the format's threshold), 1 = always where it applies,
-    // 2 = never
-    int trace_bin = 0;
     int n_cu = 256;  // compute units (rt_init)
-    // coarse depth cull of sphere candidates in bins with at least this many
-    // candidates (0 = off)
-    int coarse_cull = RT_COARSE_CULL;
-    // triangles join the depth cull in bins whose tiles keep at least this
-    // many candidates on average (0 = never)
-    int coarse_cull_tri = RT_COARSE_CULL_TRI;
-    int coarse_cull_tri_rgba8 = RT_COARSE_CULL_TRI_RGBA8;  // (RGBA8 renders)
-    int coarse_cull_tri_hit = RT_COARSE_CULL_TRI_HIT;      // (HIT renders)
-    // ... in frames whose boxes' summed area is at least this many frames
-    // (int32x4 renders; RGBA8 renders take the second gate)
-    unsigned coarse_cull_overdraw = RT_COARSE_CULL_OVERDRAW;
-    unsigned coarse_cull_overdraw_rgba8 = RT_COARSE_CULL_OVERDRAW_RGBA8;
-    unsigned coarse_cull_overdraw_hit = RT_COARSE_CULL_OVERDRAW_HIT;
-    // ... in bands of at least this many coarse bins
-    int64_t coarse_cull_tri_bins = RT_COARSE_CULL_TRI_BINS;
+    // the dispatch policy's tunables (rt_dispatch.h; the rt_debug_set_* functions)
+    rt_dispatch::Knobs knobs;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     // rt_render's kernel span: ev[1] / ev[2] ride on the first / last kernel
     // of the render (set only while rt_render_path enqueues it)
@@ -393,22 +286,10 @@ __global__ void __launch_bounds__(256) grid_check_kernel(const float4* __restric
     if (__ballot(off) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
 }
 
-// Frames of at least this many bytes take the wide tiles (auto selection):
-// 512 MiB frames store faster from wide tiles in both formats (config 5's
-// 8-rank band, config 4's half frame, a 512 MiB Texture; measured with 64x4
-// tiles), 384 MiB and smaller ones from 16x16.
-constexpr int64_t kWideTileBytes = (int64_t)1 << 29;
-
-// rt_debug_set_tile_variant: 0 = by frame size, 1 = 16x16, 2 = wide (128x2)
-bool use_wide_tiles(const rt_ctx* ctx, int32_t width, int32_t rows, int32_t fmt) {
-    const int64_t bytes = (int64_t)width * rows * (int64_t)rt_args::pixel_bytes(fmt);
-    return ctx->tile_variant == 2 || (ctx->tile_variant == 0 && bytes >= kWideTileBytes);
-}
-
 int render_launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origins,
                   int32_t width, int32_t row_begin, int32_t row_end, int32_t fmt, int32_t path,
                   void* out, hipStream_t stream, int32_t* used_path) {
-    return use_wide_tiles(ctx, width, row_end - row_begin, fmt)
+    return rt_dispatch::use_wide_tiles(ctx->knobs, width, row_end - row_begin, fmt)
                ? wide::launch(ctx, s, d, origins, width, row_begin, row_end, fmt, path, out,
                               stream, used_path)
                : tile16::launch(ctx, s, d, origins, width, row_begin, row_end, fmt, path, out,
@@ -419,8 +300,9 @@ int render_launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float*
 // render_launch() will pick (rt_reserve; rt_render before its first event).
 int reserve_launch(rt_ctx* ctx, int32_t width, int32_t rows, int32_t ns, int32_t nc,
                    int32_t fmt) {
-    return use_wide_tiles(ctx, width, rows, fmt) ? wide::reserve(ctx, ns, nc, width, rows)
-                                                 : tile16::reserve(ctx, ns, nc, width, rows);
+    return rt_dispatch::use_wide_tiles(ctx->knobs, width, rows, fmt)
+               ? wide::reserve(ctx, ns, nc, width, rows)
+               : tile16::reserve(ctx, ns, nc, width, rows);
 }
 
 // rt_render's own buffers: the scene copy and the frame it downloads from.
@@ -936,19 +818,19 @@ int rt_debug_triangle_box(const float v0[3], const float v1[3], const float v2[3
 
 int rt_debug_set_list_budget(rt_ctx* ctx, int64_t bytes) {
     if (!ctx || bytes < 0) return RT_ERR_INVALID_ARG;
-    ctx->list_budget = bytes ? bytes : (int64_t)4 << 30;
+    ctx->knobs.list_budget = bytes ? bytes : rt_dispatch::Knobs{}.list_budget;
     return RT_OK;
 }
 
 int rt_debug_set_bin_masks(rt_ctx* ctx, int enable) {
     if (!ctx) return RT_ERR_INVALID_ARG;
-    ctx->bin_masks = enable != 0;
+    ctx->knobs.bin_masks = enable != 0;
     return RT_OK;
 }
 
 int rt_debug_set_tile_variant(rt_ctx* ctx, int variant) {
     if (!ctx || variant < 0 || variant > 2) return RT_ERR_INVALID_ARG;
-    ctx->tile_variant = variant;
+    ctx->knobs.tile_variant = variant;
     return RT_OK;
 }
 
@@ -976,27 +858,30 @@ int rt_debug_tile_shape_wide(int32_t* w, int32_t* h) {
 
 int rt_debug_set_coarse_cull(rt_ctx* ctx, int enable) {
     if (!ctx) return RT_ERR_INVALID_ARG;
-    ctx->coarse_cull = enable < 0 ? RT_COARSE_CULL : enable;  // < 0: the default
+    ctx->knobs.coarse_cull = enable < 0 ? rt_dispatch::Knobs{}.coarse_cull : enable;  // < 0: the default
     return RT_OK;
 }
 
 int rt_debug_set_coarse_cull_tri(rt_ctx* ctx, int min_candidates) {
     if (!ctx) return RT_ERR_INVALID_ARG;
-    ctx->coarse_cull_tri = min_candidates < 0 ? RT_COARSE_CULL_TRI : min_candidates;
-    ctx->coarse_cull_tri_rgba8 = min_candidates < 0 ? RT_COARSE_CULL_TRI_RGBA8 : min_candidates;
-    ctx->coarse_cull_tri_hit = min_candidates < 0 ? RT_COARSE_CULL_TRI_HIT : min_candidates;
+    const rt_dispatch::Knobs def;
+    rt_dispatch::Knobs& k = ctx->knobs;
+    k.coarse_cull_tri = min_candidates < 0 ? def.coarse_cull_tri : min_candidates;
+    k.coarse_cull_tri_rgba8 = min_candidates < 0 ? def.coarse_cull_tri_rgba8 : min_candidates;
+    k.coarse_cull_tri_hit = min_candidates < 0 ? def.coarse_cull_tri_hit : min_candidates;
     return RT_OK;
 }
 
 int rt_debug_set_coarse_cull_overdraw(rt_ctx* ctx, int frames) {
     if (!ctx) return RT_ERR_INVALID_ARG;
-    ctx->coarse_cull_overdraw = frames < 0 ? RT_COARSE_CULL_OVERDRAW : (unsigned)frames;
-    ctx->coarse_cull_overdraw_rgba8 =
-        frames < 0 ? RT_COARSE_CULL_OVERDRAW_RGBA8 : (unsigned)frames;
-    ctx->coarse_cull_overdraw_hit = frames < 0 ? RT_COARSE_CULL_OVERDRAW_HIT : (unsigned)frames;
+    const rt_dispatch::Knobs def;
+    rt_dispatch::Knobs& k = ctx->knobs;
+    k.coarse_cull_overdraw = frames < 0 ? def.coarse_cull_overdraw : (unsigned)frames;
+    k.coarse_cull_overdraw_rgba8 = frames < 0 ? def.coarse_cull_overdraw_rgba8 : (unsigned)frames;
+    k.coarse_cull_overdraw_hit = frames < 0 ? def.coarse_cull_overdraw_hit : (unsigned)frames;
     // an explicit gate applies to every band size (the tests force the cull
     // on small frames this way)
-    ctx->coarse_cull_tri_bins = frames < 0 ? RT_COARSE_CULL_TRI_BINS : 0;
+    k.coarse_cull_tri_bins = frames < 0 ? def.coarse_cull_tri_bins : 0;
     return RT_OK;
 }
 
@@ -1020,20 +905,20 @@ int rt_debug_triangle_t_bounds(const float v0[3], const float v1[3], const float
 
 int rt_debug_set_small_fused(rt_ctx* ctx, int enable) {
     if (!ctx || enable < 0 || enable > 2) return RT_ERR_INVALID_ARG;
-    ctx->small_fused = enable;
+    ctx->knobs.small_fused = enable;
     return RT_OK;
 }
 
 int rt_debug_set_trace_split(rt_ctx* ctx, int waves) {
     if (!ctx || !(waves == 0 || waves == 1 || waves == 2 || waves == 4)) return RT_ERR_INVALID_ARG;
-    ctx->trace_split = waves;
+    ctx->knobs.trace_split = waves;
     return RT_OK;
 }
 
 int rt_debug_set_coarse_waves(rt_ctx* ctx, int waves) {
     if (!ctx || !(waves == 0 || waves == 1 || waves == 2 || waves == 4 || waves == 8))
         return RT_ERR_INVALID_ARG;
-    ctx->coarse_waves = waves;
+    ctx->knobs.coarse_waves = waves;
     return RT_OK;
 }
 
@@ -1051,7 +936,7 @@ int rt_debug_last_overdraw(rt_ctx* ctx, double* frames) {
 
 int rt_debug_set_trace_bin(rt_ctx* ctx, int mode) {
     if (!ctx || mode < 0 || mode > 2) return RT_ERR_INVALID_ARG;
-    ctx->trace_bin = mode;
+    ctx->knobs.trace_bin = mode;
     return RT_OK;
 }
 
@@ -1064,7 +949,7 @@ int rt_debug_set_verdict_copy(rt_ctx* ctx, int copy) {
 
 int rt_debug_set_small_path(rt_ctx* ctx, int enable) {
     if (!ctx) return RT_ERR_INVALID_ARG;
-    ctx->small_path = enable != 0;
+    ctx->knobs.small_path = enable != 0;
     return RT_OK;
 }
 

@@ -4,14 +4,10 @@
 // (RT_TILE_W = 16: 16x16 tiles; 128: 128x2 tiles), each in its own namespace;
 // rt_device.hip picks one per frame.  Not a standalone translation unit.
 //
-// Kernels (DESIGN.md §3), per frame, by scene size:
-//   <= 128 primitives, grid resident at once: frame_small_kernel (one launch)
-//   <= 512 primitives: prep_kernel -> trace_small_kernel
-//   <= 1024 primitives, box overdraw below 4 frames (int32x4) / 1 (RGBA8, HIT),
-//   frames above 4096 wave tiles: prep_kernel -> trace_bin_kernel
-//   otherwise:         prep_kernel -> coarse3_kernel -> trace3_kernel
-//                      (trace3_split_kernel on small frames)
-//   explicit origins / other directions: generic_kernel (brute force)
+// Kernels (DESIGN.md §3): six chains, listed at rt_dispatch::Decision
+// (include/rt_dispatch.h); which one a frame takes, by scene and frame size,
+// is rt_dispatch::choose() (csrc/rt_dispatch.cpp), the one statement of the
+// rules.  launch() below enqueues what it returns.
 // Every pixel-writing kernel exists per output format (kFmt): int32x4, the
 // Texture's RGBA8 word, or RT_FORMAT_HIT (rt_hit: the walk's closest and
 // colour slot, unshaded).
@@ -2514,63 +2510,27 @@ __global__ void __launch_bounds__(64 * kFusedWaves) RT_FUSED_ATTR frame_small_ke
 
 namespace {
 
-// Workspace layout of one binned launch over `rows` rows (one band of a
-// frame launch() splits): every offset and size launch() uses, so that
-// reserve() sizes exactly what the launch will ask for.
-struct Plan {
-    int n_tri, n_prims, n_cx, n_cy, n_chunks, half_cap;
-    int64_t n_coarse;
-    bool use_masks;
-    size_t tri_off, sph_off, box_off, cls_off, col_off, cnt_off, mask_off, dep_off;
-    size_t rec_need, list_need;
-};
-
-Plan plan(const rt_ctx* ctx, int n_spheres, int n_cubes, int32_t width, int32_t rows) {
-    Plan p{};
-    p.n_tri = 12 * n_cubes;
-    p.n_prims = p.n_tri + n_spheres;
-    p.n_cx = (width + kCoarseW - 1) / kCoarseW;
-    p.n_cy = (rows + kCoarseH - 1) / kCoarseH;
-    p.n_coarse = (int64_t)p.n_cx * p.n_cy;
-    // per coarse bin: candidate ids, then each tile word (half_cap each,
-    // padded by 8 so the trace's 8-wide scalar reads stay inside the bin)
-    p.half_cap = (p.n_prims + 7) / 8 * 8 + 8;
-    p.n_chunks = (p.n_prims + kPrepThreads - 1) / kPrepThreads;
-    p.use_masks = ctx->bin_masks && (int64_t)p.n_cx + p.n_cy <= kMaskBinsMax;
-    p.tri_off = 0;
-    p.sph_off = align_up(sizeof(TriRec) * (size_t)p.n_tri, 256);
-    p.box_off = p.sph_off + align_up(sizeof(SphRec) * (size_t)n_spheres, 256);
-    p.cls_off = p.box_off + align_up(sizeof(int4) * (size_t)p.n_prims, 256);
-    p.col_off = p.cls_off + align_up(sizeof(Cls) * (size_t)p.n_prims, 256);
-    p.cnt_off = p.col_off + align_up(sizeof(float4) * (size_t)(n_cubes + n_spheres), 256);
-    p.mask_off = p.cnt_off + align_up(sizeof(int) * (size_t)p.n_coarse, 256);
-    const size_t n_mask_words = p.use_masks ? (size_t)p.n_chunks * (size_t)(p.n_cx + p.n_cy) : 0;
-    p.dep_off = p.mask_off + align_up(sizeof(unsigned long long) * n_mask_words, 256);
-    p.rec_need = p.dep_off + align_up(sizeof(TriDepth) * (size_t)p.n_tri, 256);
-    p.list_need = sizeof(int) * kListStride * (size_t)p.half_cap * (size_t)p.n_coarse + 256;
-    return p;
-}
-
-// Rows per internal band of a binned launch: the whole range, or bands of
-// whole coarse rows when the candidate lists would pass the list budget or
-// the trace grid's y dimension (65535 bin rows).
-int64_t band_rows_of(const rt_ctx* ctx, int64_t n_prims, int32_t width, int32_t rows) {
-    const int64_t row_bytes =
-        4 * kListStride * ((n_prims + 7) / 8 * 8 + 8) * ((width + kCoarseW - 1) / kCoarseW);
-    const int64_t n_cy = (rows + kCoarseH - 1) / kCoarseH;
-    constexpr int64_t kMaxGridY = 65535;
-    if (n_cy > 1 && (row_bytes * n_cy > ctx->list_budget || n_cy > kMaxGridY))
-        return std::min<int64_t>(kMaxGridY, std::max<int64_t>(1, ctx->list_budget / row_bytes)) *
-               kCoarseH;
-    return rows;
-}
+// What this tile build contributes to the dispatch policy (rt_dispatch.h).
+constexpr rt_dispatch::Geometry kGeometry{
+    kCoarseW, kCoarseH, kTiles, kListStride, kPrepThreads,
+    RT_FUSED_WG, RT_FUSED_CHUNKS, RT_SMALL_CHUNKS, kBinCap, kMaskBinsMax,
+    128, 32, 32, 48};  // TriRec, SphRec, Cls, TriDepth
+static_assert(kGeometry.tri_rec_bytes == sizeof(TriRec) &&
+                  kGeometry.sph_rec_bytes == sizeof(SphRec) &&
+                  kGeometry.cls_bytes == sizeof(Cls) &&
+                  kGeometry.tri_depth_bytes == sizeof(TriDepth) && sizeof(int4) == 16 &&
+                  sizeof(float4) == 16,
+              "the workspace plan's record sizes");
 
 // Grow the binned path's workspace to what a launch over `rows` rows needs
 // (rt_reserve, and rt_render before its timed region): the launch then
-// allocates nothing.
+// allocates nothing.  The plan is the one choose() hands launch() for that
+// band: the same function of the same arguments.
 int reserve(rt_ctx* ctx, int n_spheres, int n_cubes, int32_t width, int32_t rows) {
-    const int64_t per = band_rows_of(ctx, 12 * (int64_t)n_cubes + n_spheres, width, rows);
-    const Plan p = plan(ctx, n_spheres, n_cubes, width, (int32_t)std::min<int64_t>(per, rows));
+    const int64_t per = rt_dispatch::band_rows_of(
+        kGeometry, ctx->knobs, 12 * (int64_t)n_cubes + n_spheres, width, rows);
+    const rt_dispatch::Plan p = rt_dispatch::plan(kGeometry, ctx->knobs, n_spheres, n_cubes, width,
+                                                  (int32_t)std::min<int64_t>(per, rows));
     int rc = ensure(&ctx->rec_buf, &ctx->rec_cap, p.rec_need);
     if (rc) return rc;
     return ensure(&ctx->list_buf, &ctx->list_cap, p.list_need);
@@ -2653,40 +2613,241 @@ int copy_verdict(rt_ctx* ctx, hipStream_t stream) {
     (fmt == RT_FORMAT_I32X4 ? trace3_kernel<MODE, RT_FORMAT_I32X4> \
      : fmt == RT_FORMAT_HIT ? trace3_kernel<MODE, RT_FORMAT_HIT>   \
                             : trace3_kernel<MODE, RT_FORMAT_RGBA8>)
-// Enqueue one render of rows [row_begin, row_end) on `stream`.  All scene
-// pointers are device pointers.
+#ifndef RT_SKIP_DIAG
+#define RT_SKIP_DIAG 0  // diagnostics (RT_DIAG builds): after a context's first 16 binned launches skip prep (1) / coarse (2)
+#endif
+
+// The typed pointers of one binned launch's workspace, from its plan.
+struct Workspace {
+    TriRec* tri;
+    TriDepth* tdep;
+    SphRec* sph;
+    int4* boxes;
+    Cls* cls;
+    float4* colours;
+    int* counts;
+    unsigned long long *row_masks, *col_masks;  // null without bin masks
+    int* lists;
+};
+Workspace carve(const rt_ctx* ctx, const rt_dispatch::Plan& pl) {
+    char* base = static_cast<char*>(ctx->rec_buf);
+    Workspace w;
+    w.tri = reinterpret_cast<TriRec*>(base + pl.tri_off);
+    w.tdep = reinterpret_cast<TriDepth*>(base + pl.dep_off);
+    w.sph = reinterpret_cast<SphRec*>(base + pl.sph_off);
+    w.boxes = reinterpret_cast<int4*>(base + pl.box_off);
+    w.cls = reinterpret_cast<Cls*>(base + pl.cls_off);
+    w.colours = reinterpret_cast<float4*>(base + pl.col_off);
+    w.counts = reinterpret_cast<int*>(base + pl.cnt_off);
+    w.row_masks =
+        pl.use_masks ? reinterpret_cast<unsigned long long*>(base + pl.mask_off) : nullptr;
+    w.col_masks = pl.use_masks ? w.row_masks + (size_t)pl.n_chunks * pl.n_cy : nullptr;
+    w.lists = static_cast<int*>(ctx->list_buf);
+    return w;
+}
+
+// What the kernels of one binned band launch share: the launch's arguments,
+// its decision and workspace, and its profiling events (a (start, stop) pair
+// per kernel slot: prep, coarse, trace; null without profiling).
+struct Band {
+    rt_ctx* ctx;
+    hipStream_t stream;
+    SceneDev sd;
+    float4 dir;
+    int32_t width, row_begin, row_end, fmt;
+    void* out;
+    const hipEvent_t *pe_prep, *pe_coarse, *pe_trace;
+    const rt_dispatch::Decision& dc;
+    Workspace ws;
+};
+
+// prep_kernel over the band's primitives, the first kernel of its chain.
+// `overdraw`: the slot it sums the frame's box overdraw into (null: the
+// small path, which has no use for it).
+int enqueue_prep(const Band& b, unsigned long long* overdraw) {
+    const rt_dispatch::Plan& pl = b.dc.plan;
+    const Workspace& ws = b.ws;
+    return launch_k(prep_kernel, dim3((unsigned)pl.n_chunks), dim3(kPrepThreads), b.stream,
+                    kernel_events(b.ctx, b.pe_prep, true, false), b.sd, b.dir, b.width,
+                    b.row_begin, b.row_end, ws.tri, ws.tdep, ws.sph, ws.boxes, ws.cls, ws.colours,
+                    b.ctx->flag, b.ctx->gen, ws.row_masks, ws.col_masks, pl.n_cx, pl.n_cy,
+                    overdraw);
+}
+
+// The box-overdraw slots of a launch that feeds them (flag words 2-3 / 4-5,
+// alternating per such launch): prep adds into `word`, coarse (or
+// trace_bin_kernel) reads it and zeroes `next` for the next launch.
+struct OdSlots {
+    unsigned long long *word, *next;
+};
+OdSlots take_od_slots(rt_ctx* ctx, unsigned long long area_units) {
+    ctx->od_area = area_units;  // (rt_debug_last_overdraw: the launch that sums it)
+    const unsigned slot = ctx->od_launches++ & 1u;
+    return OdSlots{reinterpret_cast<unsigned long long*>(ctx->flag + 2 + 2 * slot),
+                   reinterpret_cast<unsigned long long*>(ctx->flag + 4 - 2 * slot)};
+}
+
+// RT_KERNEL_FRAME_SMALL: frame_small_kernel alone.
+int enqueue_fused(const Band& b) {
+    rt_ctx* ctx = b.ctx;
+    const rt_dispatch::Plan& pl = b.dc.plan;
+    const int32_t fmt = b.fmt;
+    int rc;
+    if ((rc = skip_k(ctx, b.pe_prep)) || (rc = skip_k(ctx, b.pe_coarse))) return rc;
+    auto fused = pl.n_chunks == 1 ? RT_BY_FMT(frame_small_kernel, 1)
+                 : pl.n_chunks == 2 || RT_FUSED_CHUNKS <= 2
+                     ? RT_BY_FMT(frame_small_kernel, 2)
+                     : RT_BY_FMT(frame_small_kernel, RT_FUSED_CHUNKS);
+    ctx->last_kernel = RT_KERNEL_FRAME_SMALL;
+    return launch_k(fused, dim3((unsigned)(pl.n_coarse * (kTiles / kFusedWaves))),
+                    dim3(64 * kFusedWaves), b.stream, kernel_events(ctx, b.pe_trace, true, true),
+                    b.sd, b.dir, pl.n_cx, b.width, b.row_begin, b.row_end, b.out);
+}
+
+// RT_KERNEL_TRACE_SMALL: prep_kernel -> trace_small_kernel.
+int enqueue_small(const Band& b) {
+    rt_ctx* ctx = b.ctx;
+    const rt_dispatch::Plan& pl = b.dc.plan;
+    const Workspace& ws = b.ws;
+    const int32_t fmt = b.fmt;
+    int rc;
+    if ((rc = enqueue_prep(b, nullptr)) || (rc = skip_k(ctx, b.pe_coarse))) return rc;
+    // the instance with the fewest chunk slots that holds n_chunks
+    auto small = pl.n_chunks == 1   ? RT_BY_FMT(trace_small_kernel, 1)
+                 : pl.n_chunks == 2 ? RT_BY_FMT(trace_small_kernel, 2)
+                 : pl.n_chunks <= 4 || RT_SMALL_CHUNKS <= 4
+                     ? RT_BY_FMT(trace_small_kernel, 4)
+                     : RT_BY_FMT(trace_small_kernel, RT_SMALL_CHUNKS);
+    ctx->last_kernel = RT_KERNEL_TRACE_SMALL;
+    return launch_k(small, dim3((unsigned)(pl.n_coarse * kTiles)), dim3(64), b.stream,
+                    kernel_events(ctx, b.pe_trace, true, true),
+                    (const unsigned long long*)ws.row_masks,
+                    (const unsigned long long*)ws.col_masks, (const int4*)ws.boxes,
+                    (const Cls*)ws.cls, (const TriRec*)ws.tri, (const SphRec*)ws.sph,
+                    (const float4*)ws.colours, (const unsigned*)ctx->flag, ctx->gen,
+                    b.sd.n_cubes, pl.n_cx, pl.n_chunks, b.width, b.row_begin, b.row_end, b.sd,
+                    b.dir, b.out);
+}
+
+// RT_KERNEL_TRACE_BIN: prep_kernel -> trace_bin_kernel.
+int enqueue_trace_bin(const Band& b) {
+    rt_ctx* ctx = b.ctx;
+    const rt_dispatch::Plan& pl = b.dc.plan;
+    const Workspace& ws = b.ws;
+    const int32_t fmt = b.fmt;
+    const OdSlots od = take_od_slots(ctx, b.dc.area_units);
+    int rc;
+    if ((rc = enqueue_prep(b, od.word)) || (rc = skip_k(ctx, b.pe_coarse))) return rc;
+    auto bk = RT_BY_FMT(trace_bin_kernel);
+    ctx->last_kernel = RT_KERNEL_TRACE_BIN;
+    rc = launch_k(bk, dim3((unsigned)(pl.n_cx * kTiles), (unsigned)pl.n_cy), dim3(64), b.stream,
+                  kernel_events(ctx, b.pe_trace, true, true), pl.n_chunks, b.width, b.row_begin,
+                  b.row_end, ctx->gen, pl.n_cx, (const unsigned*)ctx->flag,
+                  (const unsigned long long*)ws.row_masks,
+                  (const unsigned long long*)ws.col_masks, (const int4*)ws.boxes,
+                  (const Cls*)ws.cls, (const TriRec*)ws.tri, (const SphRec*)ws.sph,
+                  (const float4*)ws.colours, b.sd, b.dir, b.out,
+                  (const unsigned long long*)od.word, od.next, b.dc.od_lo, b.dc.od_hi,
+                  verdict_word(ctx));
+    return rc ? rc : copy_verdict(ctx, b.stream);
+}
+
+// RT_KERNEL_TRACE_SPLIT, RT_KERNEL_TRACE: prep_kernel -> coarse3_kernel ->
+// trace3_split_kernel or trace3_kernel; without primitives, empty lists and
+// the trace alone.
+int enqueue_coarse(const Band& b) {
+    rt_ctx* ctx = b.ctx;
+    const rt_dispatch::Decision& dc = b.dc;
+    const rt_dispatch::Plan& pl = dc.plan;
+    const Workspace& ws = b.ws;
+    const int32_t fmt = b.fmt;
+    const int n_coarse = (int)pl.n_coarse;  // (choose(): the trace grid fits 32 bits)
+    int rc;
+    // (diagnostic builds only: the workspace keeps the last lists, so frames
+    // of an unchanged scene stay exact while the skipped kernels cost nothing)
+    const bool skip_prep = RT_SKIP_DIAG & 1 && ctx->od_launches > 16;
+    const bool skip_coarse = RT_SKIP_DIAG & 2 && ctx->od_launches > 16;
+    if (dc.feeds_overdraw) {
+        const OdSlots od = take_od_slots(ctx, dc.area_units);
+        if ((rc = skip_prep ? skip_k(ctx, b.pe_prep) : enqueue_prep(b, od.word))) return rc;
+        const int cw = dc.coarse_waves;
+        auto ck = cw == 8   ? coarse3_kernel<8>
+                  : cw == 4 ? coarse3_kernel<4>
+                  : cw == 2 ? coarse3_kernel<2>
+                            : coarse3_kernel<1>;
+        rc = skip_coarse
+                 ? skip_k(ctx, b.pe_coarse)
+                 : launch_k(ck, dim3((unsigned)n_coarse), dim3(64 * cw), b.stream,
+                            kernel_events(ctx, b.pe_coarse, true, false), (const int4*)ws.boxes,
+                            (const Cls*)ws.cls, (const SphRec*)ws.sph, (const TriDepth*)ws.tdep,
+                            pl.n_prims, pl.n_tri, pl.n_cx, n_coarse,
+                            (const unsigned long long*)ws.row_masks,
+                            (const unsigned long long*)ws.col_masks, b.row_begin, pl.half_cap,
+                            (const unsigned*)ctx->flag, ctx->gen, ctx->knobs.coarse_cull,
+                            dc.cull_tri, (const unsigned long long*)od.word, dc.od_min, od.next,
+                            ws.counts, ws.lists, dc.od_lo, dc.od_hi, verdict_word(ctx));
+        if (rc) return rc;
+    } else {
+        if ((rc = skip_k(ctx, b.pe_prep))) return rc;
+        HIP_TRY(hipMemsetAsync(ws.counts, 0, sizeof(int) * (size_t)n_coarse, b.stream));
+        if ((rc = skip_k(ctx, b.pe_coarse))) return rc;
+    }
+    const dim3 trace_grid((unsigned)(pl.n_cx * kTiles), (unsigned)pl.n_cy);
+    ctx->last_kernel = dc.chain;
+    if (dc.chain == RT_KERNEL_TRACE_SPLIT) {
+        auto sk = RT_BY_FMT(trace3_split_kernel);
+        rc = launch_k(sk, trace_grid, dim3(64 * dc.split), b.stream,
+                      kernel_events(ctx, b.pe_trace, true, true), b.sd, (const TriRec*)ws.tri,
+                      (const SphRec*)ws.sph, (const float4*)ws.colours, (const int*)ws.counts,
+                      (const int*)ws.lists, pl.half_cap, b.dir, b.width, b.row_begin, b.row_end,
+                      pl.n_cx, b.out);
+    } else {
+#if RT_DIAG
+        // diagnostics build: the trace-kernel ablations (rt_debug_set_trace_mode)
+        auto kern = ctx->trace_mode == 1   ? RT_TRACE3_BY_FMT(1)
+                    : ctx->trace_mode == 2 ? RT_TRACE3_BY_FMT(2)
+                    : ctx->trace_mode == 3 ? RT_TRACE3_BY_FMT(3)
+                    : ctx->trace_mode == 4 ? RT_TRACE3_BY_FMT(4)
+                                           : RT_TRACE3_BY_FMT(0);
+#else
+        auto kern = RT_TRACE3_BY_FMT(0);
+#endif
+        const int n_tiles_x = (b.width + kWaveTile - 1) / kWaveTile;
+        rc = launch_k(kern, trace_grid, dim3(64), b.stream,
+                      kernel_events(ctx, b.pe_trace, true, true), (const int*)ws.counts,
+                      (const int*)ws.lists, (const TriRec*)ws.tri, (const SphRec*)ws.sph, pl.n_cx,
+                      pl.half_cap, b.width, b.row_begin, b.row_end, b.sd.n_cubes,
+                      (const float4*)ws.colours, b.out, b.sd, b.dir, n_tiles_x, fmt);
+    }
+    return rc ? rc : copy_verdict(ctx, b.stream);
+}
+
+// Enqueue one render of rows [row_begin, row_end) on `stream`: the chain
+// rt_dispatch::choose() picks.  All scene pointers are device pointers.
 int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origins,
            int32_t width, int32_t row_begin, int32_t row_end, int32_t fmt,
            int32_t path, void* out, hipStream_t stream, int32_t* used_path) {
-    SceneDev sd{reinterpret_cast<const float4*>(s->sphere_origins), s->sphere_radius,
-                reinterpret_cast<const float4*>(s->sphere_colours),
-                reinterpret_cast<const float4*>(s->cube_vertices),
-                reinterpret_cast<const float4*>(s->cube_colours), s->num_spheres, s->num_cubes};
-    const float4 dir = make_float4(d[0], d[1], d[2], d[3]);
     const int32_t rows = row_end - row_begin;
-    const bool can_bin = binned_ok(d, origins);
-    if (path == RT_PATH_BINNED && !can_bin) return RT_ERR_UNSUPPORTED;
-    const bool use_bin = path == RT_PATH_BINNED || (path == RT_PATH_AUTO && can_bin);
-    if (used_path) *used_path = use_bin ? RT_PATH_BINNED : RT_PATH_GENERIC;
-    if (use_bin) {
-        // Bound the candidate-list workspace: split into bands of whole
-        // coarse rows, each a band render (bin masks per band),
-        // in order on the same stream.
-        const int64_t per =
-            band_rows_of(ctx, 12 * (int64_t)s->num_cubes + s->num_spheres, width, rows);
-        if (per < rows) {
-            const size_t px_bytes = rt_args::pixel_bytes(fmt);
-            const int32_t prof_count0 = ctx->prof_count;
-            for (int64_t rb = row_begin; rb < row_end; rb += per) {
-                const int32_t re = (int32_t)std::min<int64_t>(rb + per, row_end);
-                char* dst = static_cast<char*>(out) + (size_t)(rb - row_begin) * width * px_bytes;
-                const int rc = launch(ctx, s, d, origins, width, (int32_t)rb, re, fmt, path, dst,
-                                      stream, nullptr);
-                if (rc) return rc;
-            }
-            if (ctx->profile) ctx->prof_count = prof_count0 + 1;  // one render, summed bands
-            return RT_OK;
+    const unsigned verdict =
+        ctx->od_verdict ? *reinterpret_cast<volatile unsigned*>(ctx->od_verdict) : 0u;
+    rt_dispatch::Decision dc;
+    int rc = rt_dispatch::choose(kGeometry, ctx->knobs, ctx->n_cu, fmt, s->num_spheres,
+                                 s->num_cubes, width, rows, binned_ok(d, origins), path, verdict,
+                                 ctx->trace_mode, &dc);
+    if (rc) return rc;
+    if (used_path) *used_path = dc.chain == RT_KERNEL_GENERIC ? RT_PATH_GENERIC : RT_PATH_BINNED;
+    if (dc.band_rows < rows) {
+        // internal bands, each a band render, in order on the same stream
+        const size_t px_bytes = rt_args::pixel_bytes(fmt);
+        const int32_t prof_count0 = ctx->prof_count;
+        for (int64_t rb = row_begin; rb < row_end; rb += dc.band_rows) {
+            const int32_t re = (int32_t)std::min<int64_t>(rb + dc.band_rows, row_end);
+            char* dst = static_cast<char*>(out) + (size_t)(rb - row_begin) * width * px_bytes;
+            rc = launch(ctx, s, d, origins, width, (int32_t)rb, re, fmt, path, dst, stream, nullptr);
+            if (rc) return rc;
         }
+        if (ctx->profile) ctx->prof_count = prof_count0 + 1;  // one render, summed bands
+        return RT_OK;
     }
     const hipEvent_t* pe = nullptr;  // 6 events: prep, coarse, trace (start, stop)
     if (ctx->profile) {
@@ -2701,234 +2862,41 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
         ctx->prof_used += 6;
         ++ctx->prof_count;
     }
-    const hipEvent_t* pe_prep = pe ? pe : nullptr;
     const hipEvent_t* pe_coarse = pe ? pe + 2 : nullptr;
     const hipEvent_t* pe_trace = pe ? pe + 4 : nullptr;
-    int rc;
-    if (!use_bin) {
+    const SceneDev sd{reinterpret_cast<const float4*>(s->sphere_origins), s->sphere_radius,
+                      reinterpret_cast<const float4*>(s->sphere_colours),
+                      reinterpret_cast<const float4*>(s->cube_vertices),
+                      reinterpret_cast<const float4*>(s->cube_colours), s->num_spheres,
+                      s->num_cubes};
+    const float4 dir = make_float4(d[0], d[1], d[2], d[3]);
+    if (dc.chain == RT_KERNEL_GENERIC) {
         const int64_t n = (int64_t)width * rows;
         const int64_t blocks = std::min<int64_t>((n + kThreads - 1) / kThreads, (int64_t)1 << 20);
-        if ((rc = skip_k(ctx, pe_prep)) || (rc = skip_k(ctx, pe_coarse))) return rc;
+        if ((rc = skip_k(ctx, pe)) || (rc = skip_k(ctx, pe_coarse))) return rc;
         ctx->last_kernel = RT_KERNEL_GENERIC;
-        return launch_k(generic_kernel, dim3((unsigned)blocks), dim3(kThreads), stream, kernel_events(ctx, pe_trace, true, true),
-                        sd, dir, reinterpret_cast<const float4*>(origins), width, row_begin,
-                        row_end, fmt, out);
+        return launch_k(generic_kernel, dim3((unsigned)blocks), dim3(kThreads), stream,
+                        kernel_events(ctx, pe_trace, true, true), sd, dir,
+                        reinterpret_cast<const float4*>(origins), width, row_begin, row_end, fmt,
+                        out);
     }
-    const Plan pl = plan(ctx, s->num_spheres, s->num_cubes, width, rows);
-    const int n_tri = pl.n_tri, n_prims = pl.n_prims, n_cx = pl.n_cx, n_cy = pl.n_cy;
-    const int64_t n_coarse64 = pl.n_coarse;
-    const int n_tiles_x = (width + kWaveTile - 1) / kWaveTile;
-    // trace: one 64-lane workgroup per wave tile; AQL grid sizes are 32-bit
-    if (n_coarse64 * kTiles * 64 > (int64_t)UINT32_MAX) return RT_ERR_INVALID_ARG;
-    const int n_coarse = (int)n_coarse64;
-    const int half_cap = pl.half_cap;
-    const int n_chunks = pl.n_chunks;
-    const bool use_masks = pl.use_masks;
-    rc = ensure(&ctx->rec_buf, &ctx->rec_cap, pl.rec_need);
-    if (rc) return rc;
-    rc = ensure(&ctx->list_buf, &ctx->list_cap, pl.list_need);
-    if (rc) return rc;
-    char* base = static_cast<char*>(ctx->rec_buf);
-    TriRec* tri = reinterpret_cast<TriRec*>(base + pl.tri_off);
-    SphRec* sph = reinterpret_cast<SphRec*>(base + pl.sph_off);
-    int4* boxes = reinterpret_cast<int4*>(base + pl.box_off);
-    Cls* clsv = reinterpret_cast<Cls*>(base + pl.cls_off);
-    float4* colours = reinterpret_cast<float4*>(base + pl.col_off);
-    int* counts = reinterpret_cast<int*>(base + pl.cnt_off);
-    unsigned long long* row_masks =
-        use_masks ? reinterpret_cast<unsigned long long*>(base + pl.mask_off) : nullptr;
-    unsigned long long* col_masks = use_masks ? row_masks + (size_t)n_chunks * n_cy : nullptr;
-    TriDepth* tdep = reinterpret_cast<TriDepth*>(base + pl.dep_off);
-    int* lists = static_cast<int*>(ctx->list_buf);
+    // the workspace (grow-only: after rt_reserve, or a first frame, no allocation)
+    if ((rc = ensure(&ctx->rec_buf, &ctx->rec_cap, dc.plan.rec_need)) ||
+        (rc = ensure(&ctx->list_buf, &ctx->list_cap, dc.plan.list_need)))
+        return rc;
     // generation-stamped non-finite flag: no per-launch memset needed
     if (++ctx->gen == 0) {
         HIP_TRY(hipMemsetAsync(ctx->flag, 0, sizeof(unsigned), stream));
         ctx->gen = 1;
     }
-
-    // The one-kernel path preps the scene once per workgroup: it pays only
-    // while the whole grid is resident at once (8 four-wave workgroups per CU
-    // for one chunk, 5 for two: 28 KB of LDS each); on larger frames the
-    // preps repeat for every generation of workgroups (4096^2 with 64
-    // primitives: 46.9 -> 84.2 us per frame) and prep + trace_small wins.
-    const int64_t fused_wgs = n_coarse64 * (kTiles / RT_FUSED_WG);
-    if (n_prims > 0 && n_chunks <= RT_FUSED_CHUNKS && ctx->small_path && ctx->small_fused &&
-        ctx->trace_mode == 0 &&
-        (ctx->small_fused == 2 || fused_wgs <= (int64_t)ctx->n_cu * (n_chunks == 1 ? 8 : 5))) {
-        if ((rc = skip_k(ctx, pe_prep)) || (rc = skip_k(ctx, pe_coarse))) return rc;
-        auto fused = n_chunks == 1 ? RT_BY_FMT(frame_small_kernel, 1)
-                     : n_chunks == 2 || RT_FUSED_CHUNKS <= 2
-                         ? RT_BY_FMT(frame_small_kernel, 2)
-                         : RT_BY_FMT(frame_small_kernel, RT_FUSED_CHUNKS);
-        ctx->last_kernel = RT_KERNEL_FRAME_SMALL;
-        return launch_k(fused, dim3((unsigned)(n_coarse64 * (kTiles / kFusedWaves))),
-                        dim3(64 * kFusedWaves), stream, kernel_events(ctx, pe_trace, true, true), sd, dir, n_cx, width, row_begin,
-                        row_end, out);
+    const Band band{ctx, stream, sd, dir, width, row_begin, row_end, fmt, out,
+                    pe, pe_coarse, pe_trace, dc, carve(ctx, dc.plan)};
+    switch (dc.chain) {
+    case RT_KERNEL_FRAME_SMALL: return enqueue_fused(band);
+    case RT_KERNEL_TRACE_SMALL: return enqueue_small(band);
+    case RT_KERNEL_TRACE_BIN: return enqueue_trace_bin(band);
+    default: return enqueue_coarse(band);  // RT_KERNEL_TRACE_SPLIT, RT_KERNEL_TRACE
     }
-    if (n_prims > 0 && n_chunks <= RT_SMALL_CHUNKS && use_masks && ctx->small_path &&
-        ctx->trace_mode == 0) {
-        rc = launch_k(prep_kernel, dim3((unsigned)n_chunks), dim3(kPrepThreads), stream, kernel_events(ctx, pe_prep, true, false), sd, dir, width,
-                      row_begin, row_end, tri, tdep, sph, boxes, clsv, colours, ctx->flag, ctx->gen,
-                      row_masks, col_masks, n_cx, n_cy, (unsigned long long*)nullptr);
-        if (rc) return rc;
-        if ((rc = skip_k(ctx, pe_coarse))) return rc;
-        // the instance with the fewest chunk slots that holds n_chunks
-        auto small = n_chunks == 1   ? RT_BY_FMT(trace_small_kernel, 1)
-                     : n_chunks == 2 ? RT_BY_FMT(trace_small_kernel, 2)
-                     : n_chunks <= 4 || RT_SMALL_CHUNKS <= 4
-                         ? RT_BY_FMT(trace_small_kernel, 4)
-                         : RT_BY_FMT(trace_small_kernel, RT_SMALL_CHUNKS);
-        ctx->last_kernel = RT_KERNEL_TRACE_SMALL;
-        return launch_k(small, dim3((unsigned)(n_coarse64 * kTiles)), dim3(64), stream, kernel_events(ctx, pe_trace, true, true),
-                        (const unsigned long long*)row_masks, (const unsigned long long*)col_masks,
-                        (const int4*)boxes, (const Cls*)clsv, (const TriRec*)tri,
-                        (const SphRec*)sph, (const float4*)colours, (const unsigned*)ctx->flag,
-                        ctx->gen, s->num_cubes, n_cx, n_chunks, width, row_begin, row_end, sd,
-                        dir, out);
-    }
-    // the frame's box overdraw (64-pixel units): prep adds into one of two
-    // slots (flag words 2-3 / 4-5, alternating per binned launch), coarse (or
-    // trace_bin_kernel) reads it and zeroes the other for the next launch
-    const unsigned long long area_units =
-        ((unsigned long long)width * (unsigned long long)rows + 63ull) >> 6;
-    // the verdict's two thresholds (tenths of a frame): 1 = below
-    // RT_TRACE_BIN_OD10_RGBA8 (both formats take trace_bin_kernel), 2 = below
-    // RT_TRACE_BIN_OD10 (int32x4 only), 3 = above
-    const unsigned long long od_lo = RT_TRACE_BIN_OD10_RGBA8 * area_units / 10;
-    const unsigned long long od_hi = RT_TRACE_BIN_OD10 * area_units / 10;
-    // Binned frames without the coarse kernel (trace_bin_kernel): frames
-    // above the split-trace sizes whose last binned frame on this context
-    // had a box overdraw below the format's threshold (the coarse kernel's
-    // depth culls then save less than the kernel costs; RGBA8 frames, bound
-    // by their tests, keep the triangle cull from a lower overdraw on; HIT
-    // frames measured on RGBA8's side of int32x4's threshold: DESIGN.md §3.5)
-    const int64_t n_tiles_all = n_coarse64 * kTiles;
-    const bool bin_ok = n_prims > 0 && n_prims <= kBinCap && use_masks && ctx->trace_mode == 0;
-    const unsigned verdict =
-        ctx->od_verdict ? *reinterpret_cast<volatile unsigned*>(ctx->od_verdict) : 0u;
-    const bool use_trace_bin =
-        bin_ok && (ctx->trace_bin == 1 ||
-                   (ctx->trace_bin == 0 && n_tiles_all > RT_SPLIT2_TILES && ctx->trace_split == 0 &&
-                    (verdict == 1u || (verdict == 2u && fmt == RT_FORMAT_I32X4))));
-    if (use_trace_bin) {
-        ctx->od_area = area_units;  // (rt_debug_last_overdraw: the launch that sums it)
-        const unsigned od_slot = ctx->od_launches++ & 1u;
-        unsigned long long* od_word = reinterpret_cast<unsigned long long*>(ctx->flag + 2 + 2 * od_slot);
-        unsigned long long* od_next = reinterpret_cast<unsigned long long*>(ctx->flag + 4 - 2 * od_slot);
-        rc = launch_k(prep_kernel, dim3((unsigned)n_chunks), dim3(kPrepThreads), stream, kernel_events(ctx, pe_prep, true, false), sd, dir, width,
-                      row_begin, row_end, tri, tdep, sph, boxes, clsv, colours, ctx->flag, ctx->gen,
-                      row_masks, col_masks, n_cx, n_cy, od_word);
-        if (rc) return rc;
-        if ((rc = skip_k(ctx, pe_coarse))) return rc;
-        auto bk = RT_BY_FMT(trace_bin_kernel);
-        ctx->last_kernel = RT_KERNEL_TRACE_BIN;
-        rc = launch_k(bk, dim3((unsigned)(n_cx * kTiles), (unsigned)n_cy), dim3(64), stream,
-                        kernel_events(ctx, pe_trace, true, true), n_chunks, width, row_begin,
-                        row_end, ctx->gen, n_cx, (const unsigned*)ctx->flag,
-                        (const unsigned long long*)row_masks, (const unsigned long long*)col_masks,
-                        (const int4*)boxes, (const Cls*)clsv, (const TriRec*)tri,
-                        (const SphRec*)sph, (const float4*)colours, sd, dir, out,
-                        (const unsigned long long*)od_word, od_next, od_lo, od_hi, verdict_word(ctx));
-        if (rc) return rc;
-        return copy_verdict(ctx, stream);
-    }
-#ifndef RT_SKIP_DIAG
-#define RT_SKIP_DIAG 0  // diagnostics (RT_DIAG builds): after a context's first 16 binned launches skip prep (1) / coarse (2)
-#endif
-    // (diagnostic builds only: the workspace keeps the last lists, so frames
-    // of an unchanged scene stay exact while the skipped kernels cost nothing)
-    const bool skip_prep = RT_SKIP_DIAG & 1 && ctx->od_launches > 16;
-    const bool skip_coarse = RT_SKIP_DIAG & 2 && ctx->od_launches > 16;
-    if (n_prims > 0) {
-        // (the overdraw slots: see above; the triangle gate's threshold in
-        // the same units)
-        ctx->od_area = area_units;  // (rt_debug_last_overdraw)
-        const unsigned od_slot = ctx->od_launches++ & 1u;
-        unsigned long long* od_word = reinterpret_cast<unsigned long long*>(ctx->flag + 2 + 2 * od_slot);
-        unsigned long long* od_next = reinterpret_cast<unsigned long long*>(ctx->flag + 4 - 2 * od_slot);
-        const unsigned long long od_min =
-            (fmt == RT_FORMAT_RGBA8 ? ctx->coarse_cull_overdraw_rgba8
-             : fmt == RT_FORMAT_HIT ? ctx->coarse_cull_overdraw_hit
-                                    : ctx->coarse_cull_overdraw) *
-            area_units;
-        // triangles join the depth cull only in bands of enough coarse bins
-        // (rt_device.hip, RT_COARSE_CULL_TRI_BINS)
-        const int cull_tri = n_coarse64 < ctx->coarse_cull_tri_bins ? 0
-                             : fmt == RT_FORMAT_RGBA8          ? ctx->coarse_cull_tri_rgba8
-                             : fmt == RT_FORMAT_HIT            ? ctx->coarse_cull_tri_hit
-                                                               : ctx->coarse_cull_tri;
-        rc = skip_prep ? skip_k(ctx, pe_prep)
-                       : launch_k(prep_kernel, dim3((unsigned)n_chunks), dim3(kPrepThreads), stream,
-                                  kernel_events(ctx, pe_prep, true, false), sd, dir, width,
-                                  row_begin, row_end, tri, tdep, sph,
-                                  boxes, clsv, colours, ctx->flag, ctx->gen, row_masks, col_masks,
-                                  n_cx, n_cy, od_word);
-        if (rc) return rc;
-        // waves per coarse bin: bands of few bins run their coarse waves as
-        // one generation, each walking its bin's whole candidate list; more
-        // waves per bin shorten that (rt_debug_set_coarse_waves: 0 = by band
-        // size, else 1 / 2 / 4)
-        const int cw = ctx->coarse_waves > 0              ? ctx->coarse_waves
-                       : n_coarse64 <= RT_COARSE_W8_BINS ? 8
-                       : n_coarse64 <= RT_COARSE_W4_BINS ? 4
-                       : n_coarse64 <= RT_COARSE_W2_BINS ? 2
-                                                         : 1;
-        auto ck = cw == 8   ? coarse3_kernel<8>
-                  : cw == 4 ? coarse3_kernel<4>
-                  : cw == 2 ? coarse3_kernel<2>
-                            : coarse3_kernel<1>;
-        rc = skip_coarse ? skip_k(ctx, pe_coarse) : launch_k(ck,
-                      dim3((unsigned)n_coarse), dim3(64 * cw), stream, kernel_events(ctx, pe_coarse, true, false),
-                      (const int4*)boxes, (const Cls*)clsv, (const SphRec*)sph,
-                      (const TriDepth*)tdep, n_prims, n_tri, n_cx, n_coarse,
-                      (const unsigned long long*)row_masks,
-                      (const unsigned long long*)col_masks, row_begin, half_cap,
-                      (const unsigned*)ctx->flag, ctx->gen, ctx->coarse_cull, cull_tri,
-                      (const unsigned long long*)od_word, od_min, od_next,
-                      counts, lists, od_lo, od_hi, verdict_word(ctx));
-        if (rc) return rc;
-    } else {
-        if ((rc = skip_k(ctx, pe_prep))) return rc;
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int) * (size_t)n_coarse, stream));
-        if ((rc = skip_k(ctx, pe_coarse))) return rc;
-    }
-#if RT_DIAG
-    // diagnostics build: the trace-kernel ablations (rt_debug_set_trace_mode)
-    auto kern = ctx->trace_mode == 1   ? RT_TRACE3_BY_FMT(1)
-                : ctx->trace_mode == 2 ? RT_TRACE3_BY_FMT(2)
-                : ctx->trace_mode == 3 ? RT_TRACE3_BY_FMT(3)
-                : ctx->trace_mode == 4 ? RT_TRACE3_BY_FMT(4)
-                                       : RT_TRACE3_BY_FMT(0);
-#else
-    auto kern = RT_TRACE3_BY_FMT(0);
-#endif
-    const dim3 trace_grid((unsigned)(n_cx * kTiles), (unsigned)n_cy);
-    // Small frames: several waves per wave tile (trace3_split_kernel) while
-    // the trace grid is a fraction of the chip's wave slots: 4 waves per tile
-    // up to RT_SPLIT4_TILES tiles, 2 up to RT_SPLIT2_TILES
-    // (rt_debug_set_trace_split: 0 = that choice, 1 = never, 2 / 4 = always)
-    const int64_t n_tiles = n_coarse64 * kTiles;
-    const int split = ctx->trace_split > 0 ? ctx->trace_split
-                      : n_tiles <= RT_SPLIT4_TILES ? 4
-                      : n_tiles <= RT_SPLIT2_TILES ? 2
-                                                   : 1;
-    if (split > 1 && ctx->trace_mode == 0) {
-        ctx->last_kernel = RT_KERNEL_TRACE_SPLIT;
-        auto sk = RT_BY_FMT(trace3_split_kernel);
-        rc = launch_k(sk, trace_grid, dim3(64 * split), stream,
-                        kernel_events(ctx, pe_trace, true, true), sd, (const TriRec*)tri,
-                        (const SphRec*)sph, (const float4*)colours, (const int*)counts,
-                        (const int*)lists, half_cap, dir, width, row_begin, row_end, n_cx, out);
-        if (rc) return rc;
-        return copy_verdict(ctx, stream);
-    }
-    ctx->last_kernel = RT_KERNEL_TRACE;
-    rc = launch_k(kern, trace_grid, dim3(64), stream, kernel_events(ctx, pe_trace, true, true),
-                  (const int*)counts, (const int*)lists, (const TriRec*)tri, (const SphRec*)sph,
-                  n_cx, half_cap, width, row_begin, row_end, s->num_cubes,
-                  (const float4*)colours, out, sd, dir, n_tiles_x, fmt);
-    if (rc) return rc;
-    return copy_verdict(ctx, stream);
 }
 
 }  // namespace
