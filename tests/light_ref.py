@@ -9,10 +9,14 @@ never contracts), in the written order.
 """
 import numpy as np
 
-from hit_ref import K_FAR, REF_DIR, hit_ref
+from gpu_support import H, W, base_scene
+from hit_ref import K_FAR, REF_DIR, distinct_colours, hit_ref
 
 F32 = np.float32
 INT_MIN = -(1 << 31)
+MINUS_INF_DIR = (0.0, 0.0, -1e-4, -1.0)
+ONE_LIGHT = [(48, 40, 200, 1)]
+THREE_LIGHTS = ONE_LIGHT + [(0, 0, 50, 1), (120, 90, -20, 1)]
 _CACHE = {}
 
 
@@ -25,6 +29,34 @@ def with_lights(scene, lights):
     return type(scene)(scene.sphere_origins, scene.sphere_radius, scene.sphere_colours,
                        scene.cube_vertices, scene.cube_colours,
                        np.asarray(lights, F32).reshape(-1, 4))
+
+
+def base(pkg):
+    return distinct_colours(base_scene(pkg))
+
+
+def one_sphere(pkg, origin, radius, colour):
+    return pkg.Scene(np.array([origin], F32), np.array([radius], F32), np.array([colour], F32))
+
+
+def one_cube(pkg, ops, colour):
+    return pkg.Scene(cube_vertices=pkg.cube_packed(ops).reshape(1, 36, 4),
+                     cube_colours=np.array([colour], F32))
+
+
+def edge_scenes(pkg):
+    """(key, scene, w, h, ray_dir): the base scene and the numeric edges of
+    the shade (tests/test_hit_format.py): t = -inf, a channel past int32, a
+    NaN colour."""
+    return [
+        ("base", base(pkg), W, H, REF_DIR),
+        ("minus_inf", one_cube(pkg, [("scale", 20, 16, 1), ("translate", 16, 12, 3e38)],
+                               (1, 0.5, 0.0, 255)), 32, 24, MINUS_INF_DIR),
+        ("past_int32", one_sphere(pkg, (16, 12, -10, 1), 2e9, (1.0, 0.25, -0.25, 255)), 32, 24,
+         REF_DIR),
+        ("nan_colour", one_sphere(pkg, (16, 12, -50, 1), 9, (np.nan, 0.5, 1.0, 255)), 32, 24,
+         REF_DIR),
+    ]
 
 
 def cached_hits(oracle, key, scene, w, h, rows=None, ray_dir=REF_DIR):
@@ -144,3 +176,16 @@ def words(a):
     """Any 4-byte-element array or record array as raw uint32 words."""
     a = np.ascontiguousarray(a)
     return a.view(np.uint32).reshape(a.shape + (-1,)) if a.dtype.names else a.view(np.uint32)
+
+
+def eq(got, want):
+    """'' or a description of the first differing pixel (raw words)."""
+    a, b = words(got), words(want)
+    if a.shape != b.shape:
+        return f"shape {a.shape} vs {b.shape}"
+    bad = (a != b).reshape(got.shape[:2] + (-1,)).any(-1)
+    if not bad.any():
+        return ""
+    ys, xs = np.nonzero(bad)
+    return (f"{int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): "
+            f"{got[ys[0], xs[0]]} vs {want[ys[0], xs[0]]}")

@@ -17,19 +17,12 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from gpu_support import (FORCED_CULLS, THREADS, cube_tie_scene, device_scene, knobs, oracle_frame,
+                         tie_scene)
+
 pytestmark = pytest.mark.gpu
 
 REPO = Path(__file__).resolve().parents[1]
-THREADS = min(16, os.cpu_count() or 1)
-
-
-def _device_scene(torch, scene, dev):
-    t = {k: torch.from_numpy(np.ascontiguousarray(getattr(scene, k))).to(dev)
-         for k in ("sphere_origins", "sphere_radius", "sphere_colours", "cube_vertices",
-                   "cube_colours")}
-    ds = {k: v.data_ptr() for k, v in t.items()}
-    ds.update(num_spheres=scene.num_spheres, num_cubes=scene.num_cubes)
-    return t, ds
 
 
 def _full_frame_vs_oracle(pkg, rt, oracle, w, h, ns, nc, seed, rows, bands):
@@ -38,7 +31,7 @@ def _full_frame_vs_oracle(pkg, rt, oracle, w, h, ns, nc, seed, rows, bands):
 
     dev = torch.device("cuda:0")
     scene = pkg.Scene.synthetic(w, h, ns, nc, seed=seed, k=w / 640)
-    keep, ds = _device_scene(torch, scene, dev)
+    ds, keep = device_scene(torch, scene)
     stream = torch.cuda.current_stream().cuda_stream
     frame = torch.empty((h, w, 4), dtype=torch.int32, device=dev)
     rt.render_device(ds, w, h, (0, h), frame.data_ptr(), stream=stream)
@@ -85,7 +78,7 @@ def test_full_size_rgba8_is_packed_i32x4(pkg, rt, config):
     h = w
     dev = torch.device("cuda:0")
     scene = pkg.Scene.synthetic(w, h, ns, nc, seed=seed, k=w / 640)
-    keep, ds = _device_scene(torch, scene, dev)
+    ds, keep = device_scene(torch, scene)
     stream = torch.cuda.current_stream().cuda_stream
     full = torch.empty((h, w, 4), dtype=torch.int32, device=dev)
     tex = torch.empty((h, w), dtype=torch.int32, device=dev)
@@ -142,7 +135,7 @@ def test_device_origins_band(pkg, rt, oracle):
     ys, xs = np.mgrid[0:h, 0:w]
     org = np.stack([xs + 0.25, ys - 0.25, np.zeros_like(xs), np.ones_like(xs)],
                    -1).astype(np.float32)
-    keep, ds = _device_scene(torch, scene, dev)
+    ds, keep = device_scene(torch, scene)
     dorg = torch.from_numpy(org).to(dev)
     out = torch.empty((30, w, 4), dtype=torch.int32, device=dev)
     rt.render_device(ds, w, h, (50, 80), out.data_ptr(), origins_ptr=dorg.data_ptr(),
@@ -288,35 +281,6 @@ def test_bench_rehearsal_forced_hang(tmp_path):
     assert line["assembly"]["rccl_p2p"]["frame_check"] == "bit-exact"  # the phase before
 
 
-def _tie_scene(pkg, w, h, n, seed):
-    """Dense spheres plus exact duplicates (equal t everywhere: the first in
-    order must win, MainState.cpp:386-391) and concentric copies."""
-    rng = np.random.default_rng(seed)
-    so = np.zeros((n, 4), np.float32)
-    so[:, 0] = rng.uniform(0, w, n)
-    so[:, 1] = rng.uniform(0, h, n)
-    so[:, 2] = -rng.uniform(20, 100, n)
-    r = rng.uniform(5, 30, n).astype(np.float32) * (w / 64)
-    sc = np.concatenate([rng.uniform(0.05, 1, (n, 3)), np.full((n, 1), 255)], 1).astype(np.float32)
-    dup = rng.choice(n, n // 8, replace=False)
-    so = np.concatenate([so, so[dup]])
-    r = np.concatenate([r, r[dup]])
-    sc = np.concatenate([sc, sc[dup][:, [2, 0, 1, 3]]])
-    return pkg.Scene(so, r, sc)
-
-
-def _cube_tie_scene(pkg, w, h, seed):
-    """Dense cubes plus exact duplicates recoloured (their triangles tie at
-    every pixel: the first cube must win, MainState.cpp:386-391), and a few
-    spheres."""
-    base = pkg.Scene.synthetic(w, h, 30, 160, seed=seed, k=w / 640 * 3)
-    rng = np.random.default_rng(seed)
-    dup = rng.choice(len(base.cube_vertices), 40, replace=False)
-    cv = np.concatenate([base.cube_vertices, base.cube_vertices[dup]])
-    cc = np.concatenate([base.cube_colours, base.cube_colours[dup][:, [2, 0, 1, 3]]])
-    return pkg.Scene(base.sphere_origins, base.sphere_radius, base.sphere_colours, cv, cc)
-
-
 @pytest.mark.parametrize("case", ["dense", "dense_rgba8", "ties", "cubes_and_spheres",
                                   "dense_cubes", "cube_ties", "heavy_defaults"])
 def test_coarse_depth_cull_exact(pkg, rt, oracle, case):
@@ -329,39 +293,24 @@ def test_coarse_depth_cull_exact(pkg, rt, oracle, case):
     fmt = "rgba8" if case.endswith("rgba8") else "i32x4"
     w, h = 640, 480
     if case == "ties":
-        scene = _tie_scene(pkg, w, h, 400, 3)
+        scene = tie_scene(pkg, w, h, 400, 3)
     elif case == "cubes_and_spheres":
         scene = pkg.Scene.synthetic(w, h, 300, 40, seed=9, k=w / 640 * 4)
     elif case == "dense_cubes":  # triangles cover and drop each other
         scene = pkg.Scene.synthetic(w, h, 60, 200, seed=10, k=w / 640 * 3)
     elif case == "cube_ties":
-        scene = _cube_tie_scene(pkg, w, h, 12)
+        scene = cube_tie_scene(pkg, w, h, 12)
     elif case == "heavy_defaults":  # config 3's scene generator at 16x the objects
         scene = pkg.Scene.synthetic(w, h, 4096, 1024, seed=3, k=6.4 * w / 4096)
     else:
         scene = pkg.Scene.synthetic(w, h, 1200, 0, seed=5, k=w / 640 * 4)
-    try:
-        rt.set_coarse_cull(0)
-        rt.set_coarse_cull_tri(0)
+    with knobs(rt, coarse_cull=0, coarse_cull_tri=0):
         off, _ = rt.render(scene, w, h, fmt=fmt)
-        if case == "heavy_defaults":
-            rt.set_coarse_cull(-1)
-            rt.set_coarse_cull_tri(-1)
-        else:
-            rt.set_coarse_cull(1)  # every bin, spheres and triangles, every frame
-            rt.set_coarse_cull_tri(1)
-            rt.set_coarse_cull_overdraw(0)
+    with knobs(rt, **({} if case == "heavy_defaults" else FORCED_CULLS)):
         on, t = rt.render(scene, w, h, fmt=fmt)
-    finally:
-        rt.set_coarse_cull(-1)  # the library defaults
-        rt.set_coarse_cull_tri(-1)
-        rt.set_coarse_cull_overdraw(-1)
     assert t.path == "binned"
     assert np.array_equal(on, off)
-    want = oracle.trace(scene, w, h, threads=THREADS)
-    if fmt == "rgba8":
-        want = oracle.pack_rgba8(want)
-    assert np.array_equal(on, want)
+    assert np.array_equal(on, oracle_frame(oracle, scene, w, h, fmt=fmt, threads=THREADS))
 
 
 @pytest.mark.parametrize("case", ["ties", "cube_ties", "dense_cubes", "dense_rgba8",
@@ -376,32 +325,25 @@ def test_trace_split_exact(pkg, rt, oracle, case):
     fmt = "rgba8" if case.endswith("rgba8") else "i32x4"
     w, h, rows = 640, 480, (0, 480)
     if case == "ties":
-        scene = _tie_scene(pkg, w, h, 400, 4)
+        scene = tie_scene(pkg, w, h, 400, 4)
     elif case == "cube_ties":
-        scene = _cube_tie_scene(pkg, w, h, 13)
+        scene = cube_tie_scene(pkg, w, h, 13)
     elif case == "band":
-        scene, rows = _cube_tie_scene(pkg, w, h, 14), (77, 401)
+        scene, rows = cube_tie_scene(pkg, w, h, 14), (77, 401)
     else:
         scene = pkg.Scene.synthetic(w, h, 120, 200, seed=11, k=w / 640 * 3)
     with pytest.raises(pkg.RtError):
         rt.set_trace_split(8)  # (at most 4 waves per tile: the merge's LDS)
     frames = {}
-    try:
-        rt.set_small_path(False)  # (every case takes the binned trace)
-        if case == "wide":
-            rt.set_tile_variant(2)
-        for split in (1, 2, 4):
-            rt.set_trace_split(split)
+    fixed = dict(small_path=False)  # (every case takes the binned trace)
+    if case == "wide":
+        fixed.update(tile_variant=2)
+    for split in (1, 2, 4):
+        with knobs(rt, trace_split=split, **fixed):
             frames[split], t = rt.render(scene, w, h, rows=rows, fmt=fmt)
             assert t.path == "binned"
             assert rt.last_kernel() == ("trace3_kernel" if split == 1 else "trace3_split_kernel")
-    finally:
-        rt.set_trace_split(0)
-        rt.set_tile_variant(0)
-        rt.set_small_path(True)
-    want = oracle.trace(scene, w, h, rows=rows, threads=THREADS)
-    if fmt == "rgba8":
-        want = oracle.pack_rgba8(want)
+    want = oracle_frame(oracle, scene, w, h, rows=rows, fmt=fmt, threads=THREADS)
     for split, got in frames.items():
         assert np.array_equal(got, want), split
 
@@ -417,39 +359,26 @@ def test_coarse_waves_exact(pkg, rt, oracle, case):
     fmt = "rgba8" if case.endswith("rgba8") else "i32x4"
     w, h, rows = 640, 480, (0, 480)
     if case == "ties":
-        scene = _tie_scene(pkg, w, h, 400, 5)
+        scene = tie_scene(pkg, w, h, 400, 5)
     elif case == "cube_ties":
-        scene = _cube_tie_scene(pkg, w, h, 15)
+        scene = cube_tie_scene(pkg, w, h, 15)
     elif case == "band":
-        scene, rows = _cube_tie_scene(pkg, w, h, 16), (33, 350)
+        scene, rows = cube_tie_scene(pkg, w, h, 16), (33, 350)
     else:
         scene = pkg.Scene.synthetic(w, h, 300, 120, seed=12, k=w / 640 * 4)
     frames = {}
-    try:
-        rt.set_small_path(False)
-        if case in ("dense_culled", "dense_rgba8", "ties", "cube_ties"):
-            rt.set_coarse_cull(1)  # every bin, spheres and triangles
-            rt.set_coarse_cull_tri(1)
-            rt.set_coarse_cull_overdraw(0)
-        if case == "box_scan":
-            rt.set_bin_masks(False)
-        if case == "wide":
-            rt.set_tile_variant(2)
-        for cw in (1, 2, 4, 8):
-            rt.set_coarse_waves(cw)
+    fixed = dict(small_path=False)
+    if case in ("dense_culled", "dense_rgba8", "ties", "cube_ties"):
+        fixed.update(FORCED_CULLS)
+    if case == "box_scan":
+        fixed.update(bin_masks=False)
+    if case == "wide":
+        fixed.update(tile_variant=2)
+    for cw in (1, 2, 4, 8):
+        with knobs(rt, coarse_waves=cw, **fixed):
             frames[cw], t = rt.render(scene, w, h, rows=rows, fmt=fmt)
             assert t.path == "binned"
-    finally:
-        rt.set_coarse_waves(0)
-        rt.set_coarse_cull(-1)
-        rt.set_coarse_cull_tri(-1)
-        rt.set_coarse_cull_overdraw(-1)
-        rt.set_bin_masks(True)
-        rt.set_tile_variant(0)
-        rt.set_small_path(True)
-    want = oracle.trace(scene, w, h, rows=rows, threads=THREADS)
-    if fmt == "rgba8":
-        want = oracle.pack_rgba8(want)
+    want = oracle_frame(oracle, scene, w, h, rows=rows, fmt=fmt, threads=THREADS)
     for cw, got in frames.items():
         assert np.array_equal(got, want), cw
 
@@ -465,14 +394,9 @@ def test_trace_bin_exact(pkg, rt, oracle, case):
     fmt = "rgba8" if case.endswith("rgba8") else "i32x4"
     w, h, rows = 640, 480, (0, 480)
     if case == "ties":
-        scene = _tie_scene(pkg, w, h, 400, 6)
+        scene = tie_scene(pkg, w, h, 400, 6)
     elif case in ("cube_ties", "band"):
-        base = pkg.Scene.synthetic(w, h, 30, 60, seed=17, k=w / 640 * 3)
-        rng = np.random.default_rng(17)
-        dup = rng.choice(60, 20, replace=False)
-        cv = np.concatenate([base.cube_vertices, base.cube_vertices[dup]])
-        cc = np.concatenate([base.cube_colours, base.cube_colours[dup][:, [2, 0, 1, 3]]])
-        scene = pkg.Scene(base.sphere_origins, base.sphere_radius, base.sphere_colours, cv, cc)
+        scene = cube_tie_scene(pkg, w, h, 17, spheres=30, cubes=60, duplicates=20)
         if case == "band":
             rows = (61, 377)
     else:
@@ -482,22 +406,12 @@ def test_trace_bin_exact(pkg, rt, oracle, case):
             so[7, 0] = np.nan
             scene = pkg.Scene(so, scene.sphere_radius, scene.sphere_colours,
                               scene.cube_vertices, scene.cube_colours)
-    try:
-        rt.set_small_path(False)
-        rt.set_trace_bin(True)
-        if case == "wide":
-            rt.set_tile_variant(2)
+    with knobs(rt, small_path=False, trace_bin=1, tile_variant=2 if case == "wide" else 0):
         got, t = rt.render(scene, w, h, rows=rows, fmt=fmt)
         assert t.path == "binned"
         assert rt.last_kernel() == "trace_bin_kernel"
-    finally:
-        rt.set_trace_bin(False)
-        rt.set_tile_variant(0)
-        rt.set_small_path(True)
-    want = oracle.trace(scene, w, h, rows=rows, threads=THREADS)
-    if fmt == "rgba8":
-        want = oracle.pack_rgba8(want)
-    assert np.array_equal(got, want)
+    assert np.array_equal(got, oracle_frame(oracle, scene, w, h, rows=rows, fmt=fmt,
+                                            threads=THREADS))
 
 
 def test_render_into_registered_host_frame(pkg, rt):
@@ -523,35 +437,31 @@ def test_wide_tile_build_exact(pkg, rt, oracle, case):
     depth cull."""
     from conftest import golden_scene, load_golden
 
-    try:
-        rt.set_tile_variant(2)
-        if case == "golden":
+    if case == "golden":
+        with knobs(rt, tile_variant=2):
             for name in ("scene1_640x480", "scene3_640x480", "config2_1920x1080"):
                 g = load_golden(name)
                 got, t = rt.render(golden_scene(pkg, g), int(g["width"]), int(g["height"]))
                 assert np.array_equal(got, g["frame"]), name
-            return
-        w, h = (333, 257) if case != "edges" else (130, 67)
-        if case == "culled":
-            scene = pkg.Scene.synthetic(640, 480, 1200, 0, seed=5, k=4.0)
-            w, h = 640, 480
-        elif case == "edges":
-            scene = pkg.Scene.synthetic(w, h, 30, 12, seed=8, k=0.4)
-        else:
-            scene = pkg.Scene.synthetic(w, h, 60, 16, seed=104, k=w / 640 * 2)
-        fmt = "rgba8" if case == "rgba8" else "i32x4"
-        rows = (37, 201) if case == "bands" else (0, h)
+        return
+    w, h = (333, 257) if case != "edges" else (130, 67)
+    if case == "culled":
+        scene = pkg.Scene.synthetic(640, 480, 1200, 0, seed=5, k=4.0)
+        w, h = 640, 480
+    elif case == "edges":
+        scene = pkg.Scene.synthetic(w, h, 30, 12, seed=8, k=0.4)
+    else:
+        scene = pkg.Scene.synthetic(w, h, 60, 16, seed=104, k=w / 640 * 2)
+    fmt = "rgba8" if case == "rgba8" else "i32x4"
+    rows = (37, 201) if case == "bands" else (0, h)
+    with knobs(rt, tile_variant=2):
         wide, t = rt.render(scene, w, h, rows=rows, fmt=fmt)
         assert t.path == "binned"
-        rt.set_tile_variant(1)
+    with knobs(rt, tile_variant=1):
         narrow, _ = rt.render(scene, w, h, rows=rows, fmt=fmt)
-        assert np.array_equal(wide, narrow)
-        want = oracle.trace(scene, w, h, rows=rows, threads=THREADS)
-        if fmt == "rgba8":
-            want = oracle.pack_rgba8(want)
-        assert np.array_equal(wide, want)
-    finally:
-        rt.set_tile_variant(0)
+    assert np.array_equal(wide, narrow)
+    assert np.array_equal(wide, oracle_frame(oracle, scene, w, h, rows=rows, fmt=fmt,
+                                             threads=THREADS))
 
 
 # RT_SWEEP_SEEDS widens the sweep for one-off runs (profiles/r02/parity_sweep_4096.log)
@@ -584,35 +494,14 @@ def test_randomized_parity_sweep(pkg, rt, oracle, seed):
     split = int(rng.choice([0, 1, 2, 4]))  # waves per wave tile in the binned trace
     coarse_waves = int(rng.choice([0, 1, 2, 4, 8]))  # waves per coarse bin
     trace_bin = int(rng.choice([0, 1, 2]))  # no coarse kernel: auto / always / never
-    knobs = dict(tile=tile, small_fused=small_fused, cull_all=cull_all, bin_masks=bin_masks,
-                 split=split, coarse_waves=coarse_waves, trace_bin=trace_bin)
-    try:
-        rt.set_trace_split(split)
-        rt.set_coarse_waves(coarse_waves)
-        rt.set_trace_bin(trace_bin)
-        rt.set_tile_variant(tile)
-        rt.set_small_fused(small_fused)
-        rt.set_bin_masks(bin_masks)
-        if cull_all:  # every depth cull forced on, in every bin and frame
-            rt.set_coarse_cull(1)
-            rt.set_coarse_cull_tri(1)
-            rt.set_coarse_cull_overdraw(0)
+    drawn = dict(trace_split=split, coarse_waves=coarse_waves, trace_bin=trace_bin,
+                 tile_variant=tile, small_fused=small_fused, bin_masks=bin_masks,
+                 **(FORCED_CULLS if cull_all else {}))
+    with knobs(rt, **drawn):
         got, t = rt.render(scene, w, h, rows=rows, fmt=fmt)
-    finally:
-        rt.set_trace_split(0)
-        rt.set_coarse_waves(0)
-        rt.set_trace_bin(0)
-        rt.set_tile_variant(0)
-        rt.set_small_fused(1)
-        rt.set_bin_masks(True)
-        rt.set_coarse_cull(-1)
-        rt.set_coarse_cull_tri(-1)
-        rt.set_coarse_cull_overdraw(-1)
     assert t.path == "binned"
-    want = oracle.trace(scene, w, h, rows=rows, threads=THREADS)
-    if fmt == "rgba8":
-        want = oracle.pack_rgba8(want)
-    assert np.array_equal(got, want), (seed, w, h, ns, nc, k, rows, fmt, knobs)
+    want = oracle_frame(oracle, scene, w, h, rows=rows, fmt=fmt, threads=THREADS)
+    assert np.array_equal(got, want), (seed, w, h, ns, nc, k, rows, fmt, drawn)
 
 
 def _bench_module():

@@ -15,8 +15,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from gpu_support import FUSED_MAX_PRIMS, PATHS, base_scene, device_scene, knobs, n_prims
 from hit_ref import K_FAR, distinct_colours, hit_ref, words
-from test_gpu_numeric_edges import FUSED_MAX_PRIMS, PATHS, _set_knobs, base_scene, n_prims
 
 gpu = pytest.mark.gpu
 F32 = np.float32
@@ -48,17 +48,16 @@ def _render_paths(pkg, rt, scene, want, w, h, rows=None, fused=None, only=None, 
     (scene, want) when the scene has more than 128 primitives.  Asserts the
     kernel that ran.  Returns the number of frames compared."""
     n = 0
-    try:
-        for name, path, knobs, kernel in PATHS:
-            if only is not None and name not in only:
-                continue
-            sc, expect = scene, want
-            if name == "frame_small" and n_prims(scene) > FUSED_MAX_PRIMS:
-                sc, expect = fused
-                assert n_prims(sc) <= FUSED_MAX_PRIMS
-            if n_prims(sc) == 0 and path != "generic":
-                kernel = "trace3_kernel" if knobs.get("trace_split") == 1 else "trace3_split_kernel"
-            _set_knobs(rt, knobs)
+    for name, path, settings, kernel in PATHS:
+        if only is not None and name not in only:
+            continue
+        sc, expect = scene, want
+        if name == "frame_small" and n_prims(scene) > FUSED_MAX_PRIMS:
+            sc, expect = fused
+            assert n_prims(sc) <= FUSED_MAX_PRIMS
+        if n_prims(sc) == 0 and path != "generic":
+            kernel = "trace3_kernel" if settings.get("trace_split") == 1 else "trace3_split_kernel"
+        with knobs(rt, **settings):
             got, t = rt.render(sc, w, h, rows=rows, fmt="hit", path=path)
             where = f"{label} {name}"
             assert t.path == ("generic" if path == "generic" else "binned"), where
@@ -66,8 +65,6 @@ def _render_paths(pkg, rt, scene, want, w, h, rows=None, fused=None, only=None, 
             assert got.dtype == pkg.HIT_DTYPE and got.shape == expect.shape, where
             assert not _diff(got, expect), f"{where}: {_diff(got, expect)}"
             n += 1
-    finally:
-        _set_knobs(rt, {})
     return n
 
 
@@ -93,7 +90,7 @@ def test_every_kernel_returns_the_reference_hits(pkg, rt, oracle, w, h, rows):
 TIE_XY = (66, 32)  # the pixel where the sphere's t0 equals the cube face's t
 
 
-def tie_scene(pkg):
+def hit_tie_scene(pkg):
     """One colour for everything.  18 spheres + 7 cubes of the base scene,
     then: a copy of sphere 3 (sphere index 18), a copy of cube 1 (cube index
     7), and a sphere / cube pair of equal t: an axis-aligned cube (the unit
@@ -118,7 +115,7 @@ def tie_reference(pkg, oracle):
     """(scene, hit_ref) with the ties asserted on the reference itself."""
     if "tie" in _CACHE:
         return _CACHE["tie"]
-    s = tie_scene(pkg)
+    s = hit_tie_scene(pkg)
     w, h = 96, 80
     ref = _ref(oracle, "tie", s, w, h)
     nc = s.num_cubes
@@ -247,11 +244,7 @@ def test_render_device_band_leaves_the_rest_untouched(pkg, rt, oracle):
     dev = torch.device("cuda:0")
     scene = distinct_colours(base_scene(pkg))
     w, h, rb, re = 83, 45, 7, 38
-    keep = {k: torch.from_numpy(np.ascontiguousarray(getattr(scene, k))).to(dev)
-            for k in ("sphere_origins", "sphere_radius", "sphere_colours", "cube_vertices",
-                      "cube_colours")}
-    ds = {k: v.data_ptr() for k, v in keep.items()}
-    ds.update(num_spheres=scene.num_spheres, num_cubes=scene.num_cubes)
+    ds, keep = device_scene(torch, scene)
     sentinel = 0x5A5A5A5A
     frame = torch.full((h, w, 2), sentinel, dtype=torch.int32, device=dev)
     assert frame.data_ptr() % 8 == 0
@@ -259,12 +252,9 @@ def test_render_device_band_leaves_the_rest_untouched(pkg, rt, oracle):
     stream = torch.cuda.current_stream().cuda_stream
     for variant in (0, 2):  # by frame size (16 x 16 tiles), then the wide build
         frame.fill_(sentinel)
-        try:
-            rt.set_tile_variant(variant)
+        with knobs(rt, tile_variant=variant):
             rt.render_device(ds, w, h, (rb, re), out_ptr, fmt="hit", stream=stream)
             torch.cuda.synchronize()
-        finally:
-            rt.set_tile_variant(0)
         got = frame.cpu().numpy().view(np.uint32)
         assert (got[:rb] == sentinel).all() and (got[re:] == sentinel).all(), variant
         want = _ref(oracle, "base", scene, w, h, (rb, re))

@@ -10,27 +10,15 @@ import numpy as np
 import pytest
 
 import light_ref as lr
+from gpu_support import H, SCENE_ARRAYS, W, base_scene, device_scene
 from hit_ref import K_FAR, REF_DIR, distinct_colours
-from test_gpu_numeric_edges import H, W, base_scene
-from test_light_hits import ONE_LIGHT, THREE_LIGHTS, edge_scenes, eq
+from light_ref import ONE_LIGHT, THREE_LIGHTS, edge_scenes, eq
 
 gpu = pytest.mark.gpu
 F32 = np.float32
 PATTERN = 0x5A5A5A5A
 GUARD = 64  # int32 words in front of and behind every device output (256 B)
 WORDS = {"surface": 4, "i32x4": 4, "rgba8": 1}
-SCENE_ARRAYS = ("sphere_origins", "sphere_radius", "sphere_colours", "cube_vertices",
-                "cube_colours", "lights")
-
-
-def device_scene(torch, scene):
-    """(dict for the *_device calls, the tensors that own the memory)."""
-    keep = {k: torch.from_numpy(np.array(getattr(scene, k), F32)).to("cuda:0")
-            for k in SCENE_ARRAYS if getattr(scene, k).size}
-    ds = {k: v.data_ptr() for k, v in keep.items()}
-    ds.update(num_spheres=scene.num_spheres, num_cubes=scene.num_cubes,
-              num_lights=len(scene.lights))
-    return ds, keep
 
 
 def run_device(pkg, rt, torch, ds, hits_dev, w, rows, what, d=REF_DIR, stream=None):

@@ -19,100 +19,12 @@ conditions before it compares.
 import numpy as np
 import pytest
 
+from gpu_support import (F32, FUSED_MAX_PRIMS, H, PATHS, REF_DIR, W, base_scene, n_prims,
+                         render_all_paths)
+
 gpu = pytest.mark.gpu
 
 INT_MIN = -(1 << 31)
-W, H = 96, 80
-REF_DIR = (0.0, 0.0, -1.0, -1.0)
-F32 = np.float32
-
-
-def diff_report(got, want):
-    bad = (got != want).any(-1) if got.ndim == 3 else (got != want)
-    n = int(bad.sum())
-    if n:
-        ys, xs = np.nonzero(bad)
-        return (f"{n} pixels differ, first at (x={xs[0]}, y={ys[0]}): "
-                f"{got[ys[0], xs[0]]} vs {want[ys[0], xs[0]]}")
-    return ""
-
-
-# ---------------------------------------------------------------------------
-# The path matrix: every kernel that shades pixels, by the diagnostics knobs
-# the other GPU tests use.  (name, render path, knobs, kernel it must run)
-# ---------------------------------------------------------------------------
-_COARSE = dict(small_path=False, trace_bin=2)
-_CULLS = dict(coarse_cull=1, coarse_cull_tri=1, coarse_cull_overdraw=0)
-PATHS = [
-    ("generic", "generic", dict(), "generic_kernel"),
-    ("frame_small", "auto", dict(small_fused=2), "frame_small_kernel"),
-    ("trace_small", "auto", dict(small_fused=0), "trace_small_kernel"),
-    ("trace3", "auto", dict(_COARSE, trace_split=1), "trace3_kernel"),
-    ("trace3_culls", "auto", dict(_COARSE, trace_split=1, **_CULLS), "trace3_kernel"),
-    ("trace3_split2", "auto", dict(_COARSE, trace_split=2), "trace3_split_kernel"),
-    ("trace3_split4", "auto", dict(_COARSE, trace_split=4), "trace3_split_kernel"),
-    ("trace_bin", "auto", dict(small_path=False, trace_bin=1), "trace_bin_kernel"),
-    ("trace3_wide", "auto", dict(_COARSE, trace_split=1, tile_variant=2), "trace3_kernel"),
-    ("trace3_wide_culls", "auto", dict(_COARSE, trace_split=1, tile_variant=2, **_CULLS),
-     "trace3_kernel"),
-]
-# the library's defaults (negative: the compiled-in default of the cull knobs)
-_DEFAULTS = dict(small_path=True, small_fused=1, trace_bin=0, trace_split=0, coarse_cull=-1,
-                 coarse_cull_tri=-1, coarse_cull_overdraw=-1, tile_variant=0)
-FUSED_MAX_PRIMS = 128  # frame_small_kernel: at most two 64-primitive chunks
-
-
-def _set_knobs(rt, knobs):
-    for name, value in dict(_DEFAULTS, **knobs).items():
-        getattr(rt, "set_" + name)(value)
-
-
-def n_prims(scene):
-    return 12 * scene.num_cubes + scene.num_spheres
-
-
-def render_all_paths(rt, oracle, scene, w, h, rows=None, ray_dir=None, want=None,
-                     fused_scene=None, fused_want=None, label=""):
-    """Render `scene` through every entry of PATHS in both formats and compare
-    each frame bit for bit with the oracle's (`want`, computed here when not
-    given; RGBA8 against oracle.pack_rgba8 of it).  Asserts the path taken
-    and the kernel that ran.  frame_small_kernel takes at most 128
-    primitives: larger scenes must bring a `fused_scene` variant of at most
-    that many, rendered in its place on that path (no scene is excused).
-    An empty scene runs no small-scene kernel and no trace_bin_kernel: it
-    goes to the coarse path's trace (trace3_split_kernel on these small
-    frames unless the split knob is 1).  Knobs are restored afterwards.
-    Returns the number of frames compared."""
-    kw = dict(rows=rows, ray_dir=None if ray_dir is None else np.asarray(ray_dir, F32))
-    if want is None:
-        want = oracle.trace(scene, w, h, **kw)
-    wants = {id(scene): (want, oracle.pack_rgba8(want))}
-    if n_prims(scene) > FUSED_MAX_PRIMS:
-        assert fused_scene is not None and n_prims(fused_scene) <= FUSED_MAX_PRIMS, \
-            f"{label}: {n_prims(scene)} primitives need a <= 128-primitive variant"
-        if fused_want is None:
-            fused_want = oracle.trace(fused_scene, w, h, **kw)
-        wants[id(fused_scene)] = (fused_want, oracle.pack_rgba8(fused_want))
-    compared = 0
-    try:
-        for name, path, knobs, kernel in PATHS:
-            sc = scene
-            if name == "frame_small" and n_prims(scene) > FUSED_MAX_PRIMS:
-                sc = fused_scene
-            if n_prims(sc) == 0 and path != "generic":
-                kernel = "trace3_kernel" if knobs.get("trace_split") == 1 else "trace3_split_kernel"
-            _set_knobs(rt, knobs)
-            for fmt, expect in zip(("i32x4", "rgba8"), wants[id(sc)]):
-                got, t = rt.render(sc, w, h, fmt=fmt, path=path, **kw)
-                where = f"{label} {name}/{fmt}"
-                assert t.path == ("generic" if path == "generic" else "binned"), where
-                assert rt.last_kernel() == kernel, f"{where}: ran {rt.last_kernel()}"
-                assert got.shape == expect.shape, where
-                assert not diff_report(got, expect), f"{where}: {diff_report(got, expect)}"
-                compared += 1
-    finally:
-        _set_knobs(rt, {})
-    return compared
 
 
 # ---------------------------------------------------------------------------
@@ -121,17 +33,6 @@ def render_all_paths(rt, oracle, scene, w, h, rows=None, ray_dir=None, want=None
 def _clone(pkg, s):
     return pkg.Scene(s.sphere_origins.copy(), s.sphere_radius.copy(), s.sphere_colours.copy(),
                      s.cube_vertices.copy(), s.cube_colours.copy())
-
-
-def base_scene(pkg, fused=False):
-    """The base scene: 40 spheres + 10 cubes (160 primitives) on 96 x 80.
-    fused=True: its first 20 spheres and 8 cubes (116 primitives), the
-    variant frame_small_kernel renders; the case builders add at most 12."""
-    s = pkg.Scene.synthetic(W, H, 40, 10, seed=7, k=0.3)
-    if fused:
-        s = pkg.Scene(s.sphere_origins[:20], s.sphere_radius[:20], s.sphere_colours[:20],
-                      s.cube_vertices[:8], s.cube_colours[:8])
-    return s
 
 
 def _add_spheres(pkg, s, spheres):

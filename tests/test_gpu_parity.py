@@ -8,22 +8,10 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, SURVEY_FNV, golden_scene, load_golden, probe_fnv
-from test_gpu_numeric_edges import PATHS, render_all_paths
+from gpu_support import (EDGE_CASES, PATHS, SMALL_FIXTURES, THREADS, device_scene, diff_report,
+                         knobs, render_all_paths, scene_from)
 
 pytestmark = pytest.mark.gpu
-
-THREADS = min(16, os.cpu_count() or 1)
-SMALL_FIXTURES = ["scene1_640x480", "scene2_640x480", "scene3_640x480", "config1_512x512",
-                  "config2_1920x1080", "config2s_1920x1080"]
-
-
-def diff_report(got, want):
-    bad = (got != want).any(-1) if got.ndim == 3 else (got != want)
-    n = int(bad.sum())
-    if n:
-        ys, xs = np.nonzero(bad)
-        return f"{n} pixels differ, first at (x={xs[0]}, y={ys[0]}): {got[ys[0], xs[0]]} vs {want[ys[0], xs[0]]}"
-    return ""
 
 
 def test_fp32_selftest(rt):
@@ -143,76 +131,16 @@ def test_dense_synthetic_vs_oracle(pkg, rt, oracle, seed):
     assert not diff_report(got, want), diff_report(got, want)
 
 
-def _scene_from(pkg, spheres=(), cubes=()):
-    so = np.array([s[0] for s in spheres], np.float32).reshape(-1, 4)
-    sr = np.array([s[1] for s in spheres], np.float32)
-    sc = np.array([s[2] for s in spheres], np.float32).reshape(-1, 4)
-    cv = np.array([pkg.cube_packed(c[0]) for c in cubes], np.float32).reshape(-1, 36, 4)
-    cc = np.array([c[1] for c in cubes], np.float32).reshape(-1, 4)
-    return pkg.Scene(so, sr, sc, cv, cc)
-
-
-EDGE_CASES = {
-    "empty": dict(),
-    "spheres_only": dict(spheres=[((40, 30, -50, 1), 20, (1, .5, .25, 255)),
-                                  ((60, 30, -20, 1), 25, (.1, .9, .3, 255))]),
-    "cubes_only": dict(cubes=[([("scale", 15, 15, 15), ("rotate", .3, .7, .1),
-                                ("translate", 50, 35, -40)], (.2, .4, .9, 255))]),
-    # origin inside a sphere and cubes crossing z = 0: t < 0, values > 255
-    "behind_origin": dict(spheres=[((50, 40, -10, 1), 40, (1, 1, 1, 255))],
-                          cubes=[([("scale", 30, 30, 30), ("rotate", .5, .2, .9),
-                                   ("translate", 30, 30, 5)], (1, .5, 1, 255))]),
-    # far objects: shade < 0, negative int channels
-    "far": dict(spheres=[((50, 40, -900, 1), 30, (1, 1, 1, 255))],
-                cubes=[([("scale", 20, 20, 20), ("rotate", .1, .2, .3),
-                         ("translate", 20, 20, -2000)], (1, 1, 1, 255))]),
-    # spheres in front of the origin plane never hit (tca < 0), and off-screen
-    "culled": dict(spheres=[((50, 40, 30, 1), 30, (1, 1, 1, 255)),
-                            ((-500, 40, -30, 1), 30, (1, 1, 1, 255)),
-                            ((50, 4000, -30, 1), 30, (1, 1, 1, 255))]),
-    # edge-on slivers: |det| near EPSILON, culling bound must stay conservative
-    "slivers": dict(cubes=[([("scale", 40, 1e-3, 40), ("translate", 50, 40.5, -30)],
-                            (1, .2, .2, 255)),
-                           ([("scale", 40, 1e-3, 40), ("rotate", 1e-4, 0, 0.3),
-                             ("translate", 50, 30, -30)], (1, .6, .2, 255)),
-                           ([("scale", 1e-4, 30, 30), ("rotate", 0, 1e-5, 0),
-                             ("translate", 30, 20, -30)], (.2, 1, .2, 255)),
-                           ([("scale", 3e-3, 3e-3, 3e-3), ("translate", 10, 10, -5)],
-                            (.7, .7, .2, 255)),
-                           ([("scale", 25, 25, 2e-6), ("translate", 70, 50, -30)],
-                            (.2, .2, 1, 255))]),
-    # exact ties: identical spheres / duplicate cubes, first primitive must win
-    "ties": dict(spheres=[((50, 40, -50, 1), 20, (1, 0, 0, 255)),
-                          ((50, 40, -50, 1), 20, (0, 1, 0, 255))],
-                 cubes=[([("scale", 10, 10, 10), ("translate", 20, 20, -30)], (0, 0, 1, 255)),
-                        ([("scale", 10, 10, 10), ("translate", 20, 20, -30)], (1, 1, 0, 255))]),
-    # sphere origin w != 1 and a zero radius
-    "odd_w": dict(spheres=[((50, 40, -50, 3), 20, (1, .3, .3, 255)),
-                           ((20, 20, -50, 1), 0, (1, 1, 1, 255))]),
-    # depth culling: a big front sphere, layers behind it (culled once the
-    # tile is covered), spheres whose lower bound equals the front depth,
-    # a later nearer one that must still win, t0 == 0 and t < 0 spheres
-    "depth_layers": dict(spheres=[((50, 40, -30, 1), 60, (1, .2, .2, 255))] +
-                         [((45 + 3 * i, 35 + 2 * i, -30 - i, 1), 20 + i, (.2, 1, .2, 255))
-                          for i in range(12)] +
-                         [((50, 40, -30, 1), 60, (0, 0, 1, 255)),
-                          ((50, 40, -90, 1), 60, (0, 1, 1, 255)),
-                          ((30, 30, -95, 1), 90, (1, 1, 0, 255)),
-                          ((60, 50, -10, 1), 10, (1, 0, 1, 255)),
-                          ((20, 60, -4, 1), 4, (.5, .5, .5, 255))]),
-}
-
-
 @pytest.mark.parametrize("case", sorted(EDGE_CASES))
 @pytest.mark.parametrize("size", [(101, 77), (1, 1), (64, 64)])
 def test_edge_cases(pkg, rt, oracle, case, size):
     """Every edge scene through every kernel of the path matrix
-    (test_gpu_numeric_edges.PATHS: generic, both small-scene kernels,
+    (gpu_support.PATHS: generic, both small-scene kernels,
     trace3_kernel with and without the forced depth culls, the split trace,
     trace_bin_kernel, the wide tile build) in both formats, the kernel that
     ran asserted, each frame the oracle's bit for bit."""
     w, h = size
-    scene = _scene_from(pkg, **EDGE_CASES[case])
+    scene = scene_from(pkg, **EDGE_CASES[case])
     n = render_all_paths(rt, oracle, scene, w, h, label=f"{case} {w}x{h}")
     assert n == 2 * len(PATHS)
 
@@ -220,34 +148,26 @@ def test_edge_cases(pkg, rt, oracle, case, size):
 def test_nonfinite_scene_falls_back_exactly(pkg, rt, oracle):
     """NaN / inf scene data: the binned launch detects it on the device and
     runs the verbatim reference algorithm (no CPU fallback)."""
-    scene = _scene_from(pkg, spheres=[((30, 30, -40, 1), np.inf, (1, .5, .5, 255)),
-                                      ((60, 30, -40, 1), 10, (.5, 1, .5, 255))],
-                        cubes=[([("scale", 10, 10, 10), ("translate", 40, 40, -30)],
-                                (.5, .5, 1, 255))])
+    scene = scene_from(pkg, spheres=[((30, 30, -40, 1), np.inf, (1, .5, .5, 255)),
+                                     ((60, 30, -40, 1), 10, (.5, 1, .5, 255))],
+                       cubes=[([("scale", 10, 10, 10), ("translate", 40, 40, -30)],
+                               (.5, .5, 1, 255))])
     scene.cube_vertices[0, 4, 0] = np.nan
     want = oracle.trace(scene, 90, 70)
-    try:
-        for small, fused in ((True, True), (True, False), (False, False)):
-            rt.set_small_path(small)
-            rt.set_small_fused(2 if fused else 0)
+    for small, fused in ((True, True), (True, False), (False, False)):
+        with knobs(rt, small_path=small, small_fused=2 if fused else 0):
             got, t = rt.render(scene, 90, 70)
             assert t.path == "binned"
             assert np.array_equal(got, want), (small, fused)
-    finally:
-        rt.set_small_path(True)
-        rt.set_small_fused(1)
     # a second chunk's primitive non-finite (frame_small_kernel's second
     # prep wave)
     big = pkg.Scene.synthetic(90, 70, 100, 0, seed=4, k=0.2)
     big.sphere_radius[90] = np.nan
     want = oracle.trace(big, 90, 70)
-    try:
-        for fused in (True, False):
-            rt.set_small_fused(2 if fused else 0)
+    for fused in (True, False):
+        with knobs(rt, small_fused=2 if fused else 0):
             got, _ = rt.render(big, 90, 70)
             assert np.array_equal(got, want), fused
-    finally:
-        rt.set_small_fused(1)
 
 
 @pytest.mark.parametrize("w,h,ns,nc,k", [(512, 512, 4, 1, 1.0), (1920, 1080, 16, 4, 3.0),
@@ -270,10 +190,8 @@ def test_small_scene_path(pkg, rt, oracle, w, h, ns, nc, k):
     scene = pkg.Scene.synthetic(w, h, ns, nc, seed=w + ns, k=k)
     assert ns + 12 * nc <= 512
     frames = {}
-    try:
-        for small, fused in ((True, True), (True, False), (False, False)):
-            rt.set_small_path(small)
-            rt.set_small_fused(2 if fused else 0)
+    for small, fused in ((True, True), (True, False), (False, False)):
+        with knobs(rt, small_path=small, small_fused=2 if fused else 0):
             full, t = rt.render(scene, w, h)
             assert t.path == "binned"
             band, _ = rt.render(scene, w, h, rows=(h // 3, h - h // 5))
@@ -281,9 +199,6 @@ def test_small_scene_path(pkg, rt, oracle, w, h, ns, nc, k):
             tex, _ = rt.render(scene, w, h, fmt="rgba8")
             assert np.array_equal(tex, pkg.pack_rgba8(full))
             frames[small, fused] = full
-    finally:
-        rt.set_small_path(True)
-        rt.set_small_fused(1)
     assert np.array_equal(frames[True, True], frames[False, False])
     assert np.array_equal(frames[True, False], frames[False, False])
     frames[True] = frames[True, True]
@@ -325,8 +240,7 @@ def test_config3_full_frame(pkg, oracle, trace_bin, kernel):
     g = load_golden("config3_4096x4096")
     scene = golden_scene(pkg, g)
     w, h = int(g["width"]), int(g["height"])
-    with pkg.RayTracer(0) as fresh:
-        fresh.set_trace_bin(trace_bin)
+    with pkg.RayTracer(0) as fresh, knobs(fresh, trace_bin=trace_bin):
         frame, t = fresh.render(scene, w, h)
         assert t.path == "binned"
         assert fresh.last_kernel() == kernel
@@ -388,17 +302,13 @@ def test_device_api_into_torch(pkg, rt):
     torch = pytest.importorskip("torch")
     g = load_golden("scene1_640x480")
     scene = golden_scene(pkg, g)
-    dev = torch.device("cuda:0")
-    t = {k: torch.from_numpy(np.ascontiguousarray(getattr(scene, k))).to(dev)
-         for k in ("sphere_origins", "sphere_radius", "sphere_colours", "cube_vertices",
-                   "cube_colours")}
-    ds = {k: v.data_ptr() for k, v in t.items()}
-    ds.update(num_spheres=scene.num_spheres, num_cubes=scene.num_cubes)
-    out = torch.empty((480, 640, 4), dtype=torch.int32, device=dev)
+    ds, keep = device_scene(torch, scene)
+    out = torch.empty((480, 640, 4), dtype=torch.int32, device="cuda:0")
     stream = torch.cuda.current_stream().cuda_stream
     rt.render_device(ds, 640, 480, (0, 480), out.data_ptr(), stream=stream)
     torch.cuda.synchronize()
     assert np.array_equal(out.cpu().numpy(), g["frame"])
+    del keep
 
 
 def test_candidate_lists_larger_than_lds_round(pkg, rt, oracle):
@@ -439,13 +349,6 @@ def test_headless_cpp_driver(pkg, scene_id, tmp_path):
     assert np.array_equal(rgb, g["frame"][..., :3].astype(np.uint8))
 
 
-def _fnv1a64_words(words: np.ndarray) -> int:
-    h = 0xcbf29ce484222325
-    for w in words.ravel().tolist():
-        h = ((h ^ (w & 0xffffffff)) * 0x100000001b3) & 0xffffffffffffffff
-    return h
-
-
 @pytest.mark.parametrize("scene_id,bands", [(1, 1), (2, 1), (3, 1), (3, 3)])
 def test_headless_cpp_driver_rgba8(pkg, oracle, scene_id, bands, tmp_path):
     """The C++ host asking for the Texture format (rt_headless --format rgba8:
@@ -468,7 +371,7 @@ def test_headless_cpp_driver_rgba8(pkg, oracle, scene_id, bands, tmp_path):
                         "--bands", str(bands), "--ppm", str(ppm)],
                        capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode == 0, r.stderr
-    assert f"rgba8 fnv1a64 {_fnv1a64_words(want):016x}" in r.stdout, r.stdout
+    assert f"rgba8 fnv1a64 {pkg.fnv1a64(want):016x}" in r.stdout, r.stdout
     data = ppm.read_bytes()
     header = b"P6\n640 480\n255\n"
     assert data.startswith(header)
@@ -628,17 +531,14 @@ def test_bin_masks_match_box_scan(pkg, rt, oracle, w, h, ns, nc, k):
     the scan of every box (the extreme-aspect path), on full frames and row
     bands, and both match the oracle."""
     scene = pkg.Scene.synthetic(w, h, ns, nc, seed=w + h, k=k)
-    try:
-        frames = {}
-        for masks in (True, False):
-            rt.set_bin_masks(masks)
+    frames = {}
+    for masks in (True, False):
+        with knobs(rt, bin_masks=masks):
             full, t = rt.render(scene, w, h)
             assert t.path == "binned"
             band, _ = rt.render(scene, w, h, rows=(h // 3, h - h // 5))
             assert np.array_equal(band, full[h // 3:h - h // 5])
             frames[masks] = full
-    finally:
-        rt.set_bin_masks(True)
     assert np.array_equal(frames[True], frames[False])
     want = oracle.trace(scene, w, h, threads=THREADS)
     assert not diff_report(frames[True], want), diff_report(frames[True], want)
@@ -762,9 +662,8 @@ def test_list_budget_bands(pkg, rt, oracle):
     full8, _ = rt.render(scene, w, h, fmt="rgba8")
     n_prims = 12 * 40 + 500
     row_bytes = 8 * ((n_prims + 7) // 8 * 8 + 8) * ((w + 63) // 64)
-    try:
-        for budget in (1, 2 * row_bytes, 5 * row_bytes + 1):
-            rt.set_list_budget(budget)
+    for budget in (1, 2 * row_bytes, 5 * row_bytes + 1):
+        with knobs(rt, list_budget=budget):
             got, t = rt.render(scene, w, h)
             assert t.path == "binned"
             assert np.array_equal(got, full), budget
@@ -772,16 +671,15 @@ def test_list_budget_bands(pkg, rt, oracle):
             assert np.array_equal(got, full[50:700]), budget
             got, _ = rt.render(scene, w, h, fmt="rgba8")
             assert np.array_equal(got, full8), budget
-        # profiling counts the banded frame as one render, its bands summed
-        rt.set_list_budget(2 * row_bytes)
+    # profiling counts the banded frame as one render, its bands summed
+    with knobs(rt, list_budget=2 * row_bytes):
         rt.profile(True)
-        rt.render(scene, w, h)
-        prof = rt.profile_read()
-        rt.profile(False)
+        try:
+            rt.render(scene, w, h)
+            prof = rt.profile_read()
+        finally:
+            rt.profile(False)
         assert prof["renders"] == 1 and prof["trace_ms"] > 0, prof
-    finally:
-        rt.profile(False)
-        rt.set_list_budget(0)
     want = oracle.trace(scene, w, h, threads=THREADS)
     assert not diff_report(full, want), diff_report(full, want)
 
@@ -799,20 +697,18 @@ def test_profile_slots_of_skipped_kernels(pkg, rt):
              (big, "binned", (True, True, True), True),
              (pkg.Scene(), "binned", (False, False, True), True),
              (small, "generic", (False, False, True), True)]
-    try:
-        for scene, path, ran, fused in cases:
-            rt.set_small_fused(2 if fused else 0)
+    for scene, path, ran, fused in cases:
+        with knobs(rt, small_fused=2 if fused else 0):
             rt.profile(True)
-            rt.render(scene, 640, 480, path=path)
-            rt.render(scene, 640, 480, path=path)
-            prof = rt.profile_read()
-            rt.profile(False)
-            assert prof["renders"] == 2, prof
-            for key, on in zip(("prep_ms", "bin_ms", "trace_ms"), ran):
-                assert (prof[key] > 0) == on, (path, key, prof)
-    finally:
-        rt.profile(False)
-        rt.set_small_fused(1)
+            try:
+                rt.render(scene, 640, 480, path=path)
+                rt.render(scene, 640, 480, path=path)
+                prof = rt.profile_read()
+            finally:
+                rt.profile(False)
+        assert prof["renders"] == 2, prof
+        for key, on in zip(("prep_ms", "bin_ms", "trace_ms"), ran):
+            assert (prof[key] > 0) == on, (path, key, prof)
 
 
 @pytest.mark.parametrize("n_ctx", [1, 2, 3, 5])
@@ -931,8 +827,7 @@ def test_trace_bin_automatic_choice(pkg, oracle):
     want_low = oracle.trace(low, 2048, 2048, threads=THREADS)
     want_high = oracle.trace(high, 2048, 2048, threads=THREADS)
     for mode, first in ((0, "trace3_kernel"), (1, "trace_bin_kernel"), (2, "trace3_kernel")):
-        with pkg.RayTracer(0) as fresh:
-            fresh.set_trace_bin(mode)
+        with pkg.RayTracer(0) as fresh, knobs(fresh, trace_bin=mode):
             f, _ = fresh.render(low, 2048, 2048)
             assert fresh.last_kernel() == first, mode
             assert np.array_equal(f, want_low), mode
@@ -1037,11 +932,8 @@ def test_last_kernel_names_the_path_taken(pkg, rt, oracle):
     for scene, w, h, path, want in cases:
         # (binned frames of <= 1024 primitives: trace_bin_kernel forced on for
         # "bin", off otherwise; its automatic choice is tested below)
-        rt.set_trace_bin(1 if path == "bin" else 2)
-        try:
+        with knobs(rt, trace_bin=1 if path == "bin" else 2):
             frame, _ = rt.render(scene, w, h, path="auto" if path == "bin" else path)
-        finally:
-            rt.set_trace_bin(0)
         assert rt.last_kernel() == want, (w, h, scene.num_spheres, scene.num_cubes)
         if w * h <= 256 * 128:
             assert np.array_equal(frame, oracle.trace(scene, w, h))

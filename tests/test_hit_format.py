@@ -15,8 +15,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from gpu_support import H, W, base_scene, diff_report
 from hit_ref import K_FAR, REF_DIR, distinct_colours, hit_ref, words
-from test_gpu_numeric_edges import H, W, base_scene, diff_report
 
 REPO = Path(__file__).resolve().parents[1]
 F32 = np.float32

@@ -14,36 +14,18 @@ import numpy as np
 import pytest
 
 import light_ref as lr
-from hit_ref import K_FAR, REF_DIR, distinct_colours, hit_ref
-from test_gpu_numeric_edges import H, W, base_scene
+from gpu_support import H, W
+from hit_ref import K_FAR, REF_DIR, hit_ref
+from light_ref import ONE_LIGHT, THREE_LIGHTS, base, edge_scenes, eq, one_cube, one_sphere
 
 REPO = Path(__file__).resolve().parents[1]
 F32 = np.float32
 INT_MIN = -(1 << 31)
 UP_DIR = (0.0, 0.0, 1.0, 0.0)
-ONE_LIGHT = [(48, 40, 200, 1)]
-THREE_LIGHTS = ONE_LIGHT + [(0, 0, 50, 1), (120, 90, -20, 1)]
 # (key, w, h, rows, ray_dir): the frames of the base scene
 FRAMES = [("96x80", W, H, None, REF_DIR), ("83x45_rows_7_38", 83, 45, (7, 38), REF_DIR),
           ("96x80_dir_0_0_1_0", W, H, None, UP_DIR)]
 FRAME_IDS = [f[0] for f in FRAMES]
-
-
-def base(pkg):
-    return distinct_colours(base_scene(pkg))
-
-
-def eq(got, want):
-    """'' or a description of the first differing pixel (raw words)."""
-    a, b = lr.words(got), lr.words(want)
-    if a.shape != b.shape:
-        return f"shape {a.shape} vs {b.shape}"
-    bad = (a != b).reshape(got.shape[:2] + (-1,)).any(-1)
-    if not bad.any():
-        return ""
-    ys, xs = np.nonzero(bad)
-    return (f"{int(bad.sum())} pixels differ, first at (x={xs[0]}, y={ys[0]}): "
-            f"{got[ys[0], xs[0]]} vs {want[ys[0], xs[0]]}")
 
 
 def classes(scene, hits):
@@ -93,33 +75,6 @@ def test_hit_surfaces_equal_the_restatement(pkg, oracle, key, w, h, rows, d):
 
 
 # --- 2. zero lights: the reference's frame ------------------------------------
-def _one_sphere(pkg, origin, radius, colour):
-    return pkg.Scene(np.array([origin], F32), np.array([radius], F32), np.array([colour], F32))
-
-
-def _one_cube(pkg, ops, colour):
-    return pkg.Scene(cube_vertices=pkg.cube_packed(ops).reshape(1, 36, 4),
-                     cube_colours=np.array([colour], F32))
-
-
-MINUS_INF_DIR = (0.0, 0.0, -1e-4, -1.0)
-
-
-def edge_scenes(pkg):
-    """(key, scene, w, h, ray_dir): the base scene and the numeric edges of
-    the shade (tests/test_hit_format.py): t = -inf, a channel past int32, a
-    NaN colour."""
-    return [
-        ("base", base(pkg), W, H, REF_DIR),
-        ("minus_inf", _one_cube(pkg, [("scale", 20, 16, 1), ("translate", 16, 12, 3e38)],
-                                (1, 0.5, 0.0, 255)), 32, 24, MINUS_INF_DIR),
-        ("past_int32", _one_sphere(pkg, (16, 12, -10, 1), 2e9, (1.0, 0.25, -0.25, 255)), 32, 24,
-         REF_DIR),
-        ("nan_colour", _one_sphere(pkg, (16, 12, -50, 1), 9, (np.nan, 0.5, 1.0, 255)), 32, 24,
-         REF_DIR),
-    ]
-
-
 @pytest.mark.parametrize("i", range(4), ids=["base", "minus_inf", "past_int32", "nan_colour"])
 def test_zero_lights_is_the_reference_frame(pkg, oracle, i):
     key, scene, w, h, d = edge_scenes(pkg)[i]
@@ -172,7 +127,7 @@ def test_axis_aligned_face_normal_and_triangles(pkg, oracle):
     """A cube of scale (15, 15, 10) at z = -50: the face at z = -40 is seen
     head on, its normal after facing is exactly (0, 0, 1), and the pixels
     split between that face's two triangles."""
-    scene = _one_cube(pkg, [("scale", 15, 15, 10), ("translate", 32, 24, -50)], (1, 1, 1, 255))
+    scene = one_cube(pkg, [("scale", 15, 15, 10), ("translate", 32, 24, -50)], (1, 1, 1, 255))
     hits = hit_ref(oracle, scene, 64, 48)
     on = hits["object"] == 0
     assert on.sum() > 500 and (hits["t"][on] == 40).all()
@@ -187,7 +142,7 @@ def test_axis_aligned_face_normal_and_triangles(pkg, oracle):
 
 
 def sphere_and_light(pkg, light_z):
-    s = _one_sphere(pkg, (32, 24, -50, 1), 20, (1.0, 0.5, 0.25, 255))
+    s = one_sphere(pkg, (32, 24, -50, 1), 20, (1.0, 0.5, 0.25, 255))
     return lr.with_lights(s, [(32, 24, light_z, 1)])
 
 

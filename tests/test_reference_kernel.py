@@ -19,8 +19,8 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from gpu_support import EDGE_CASES, SMALL_FIXTURES, diff_report, scene_from
 from ref_kernel import CODE_OBJECT, ReferenceKernel
-from test_gpu_parity import EDGE_CASES, SMALL_FIXTURES, _scene_from, diff_report
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +67,7 @@ def test_reference_kernel_golden_scenes(refk, oracle, name):
 def test_reference_kernel_edge_cases(pkg, refk, oracle, case):
     """Ties (first primitive wins), t < 0, t0 == 0, far shades < 0, values
     > 255, slivers, w != 1, empty scenes."""
-    scene = _scene_from(pkg, **EDGE_CASES[case])
+    scene = scene_from(pkg, **EDGE_CASES[case])
     d = oracle.ray_dir()
     got = refk.trace(scene, 101, 77, d)
     want = oracle.trace_cl_gfx950(scene, 101, 77, ray_dir=d)
