@@ -20,10 +20,11 @@ def hit_dtype():
     return np.dtype([("t", "<f4"), ("object", "<i4")])
 
 
-def hit_ref(oracle, scene, w, h, rows=None, ray_dir=REF_DIR):
+def hit_ref(oracle, scene, w, h, rows=None, ray_dir=REF_DIR, x_begin=0):
     """(rows x w) records (t, object) of the reference's implicit-origin
     frame: object = cube index, or num_cubes + sphere index, or -1 beside
-    t = 300000 where nothing was hit."""
+    t = 300000 where nothing was hit.  `x_begin`: the frame column of the
+    first of the `w` columns computed (a window of a wider frame)."""
     rb, re = rows if rows is not None else (0, h)
     n = re - rb
     d = np.ascontiguousarray(ray_dir, F32)
@@ -33,7 +34,8 @@ def hit_ref(oracle, scene, w, h, rows=None, ray_dir=REF_DIR):
     for c in range(len(cubes)):
         for k in range(0, 36, 3):
             # intersectTri's fp64 t (NaN: no hit), then `(float)t < closest`
-            t = oracle.tri_t_grid(cubes[c, k], cubes[c, k + 1], cubes[c, k + 2], d, 0, rb, w, n)
+            t = oracle.tri_t_grid(cubes[c, k], cubes[c, k + 1], cubes[c, k + 2], d, x_begin,
+                                  rb, w, n)
             with np.errstate(over="ignore", invalid="ignore"):
                 tf = t.astype(F32)
                 take = ~np.isnan(t) & (tf < closest)
@@ -44,10 +46,16 @@ def hit_ref(oracle, scene, w, h, rows=None, ray_dir=REF_DIR):
     for i in range(len(radius)):
         # pixels the sphere test does not leave early (everywhere else it
         # returns the 0 that collide skips)
-        marked = oracle.sphere_grid(origins[i], radius[i], d, 0, rb, w, n)
+        marked = oracle.sphere_grid(origins[i], radius[i], d, x_begin, rb, w, n)
+        # oracle.intersect_sphere per marked pixel, without its per-call array
+        # conversions (some directions mark every pixel of every sphere)
+        org = np.array([0.0, 0.0, 0.0, 1.0], F32)
+        call, po, pd, pc = (oracle.lib.orc_intersect_sphere, org.ctypes.data, d.ctypes.data,
+                            origins[i].ctypes.data)
+        r = float(radius[i])
         for y, x in zip(*np.nonzero(marked)):
-            dist = F32(oracle.intersect_sphere((F32(x), F32(rb + y), 0.0, 1.0), d, float(radius[i]),
-                                               origins[i]))
+            org[0], org[1] = x_begin + x, rb + y
+            dist = F32(call(po, pd, r, pc))
             if dist == 0.0:
                 continue
             if dist < closest[y, x]:

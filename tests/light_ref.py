@@ -59,11 +59,12 @@ def edge_scenes(pkg):
     ]
 
 
-def cached_hits(oracle, key, scene, w, h, rows=None, ray_dir=REF_DIR):
-    """hit_ref, computed once per key and read-only."""
-    k = ("hits", key, w, h, rows, tuple(ray_dir))
+def cached_hits(oracle, key, scene, w, h, rows=None, ray_dir=REF_DIR, x_begin=0):
+    """hit_ref, computed once per key and read-only.  (The key holds the
+    direction's words: -0.0 and 0.0 are different frames' keys.)"""
+    k = ("hits", key, w, h, rows, np.asarray(ray_dir, F32).tobytes(), x_begin)
     if k not in _CACHE:
-        r = hit_ref(oracle, scene, w, h, rows=rows, ray_dir=ray_dir)
+        r = hit_ref(oracle, scene, w, h, rows=rows, ray_dir=ray_dir, x_begin=x_begin)
         r.setflags(write=False)
         _CACHE[k] = r
     return _CACHE[k]
@@ -74,26 +75,29 @@ def _unit(mx, my, mz):
     return mx / length, my / length, mz / length
 
 
-def hit_points(hits, row_begin, ray_dir):
-    """p = (x + t*d.x, y + t*d.y, 0 + t*d.z) per pixel, three (rows x w) arrays."""
+def hit_points(hits, row_begin, ray_dir, x_begin=0):
+    """p = (x + t*d.x, y + t*d.y, 0 + t*d.z) per pixel, three (rows x w) arrays.
+    `x_begin`: the frame column of hits[:, 0]."""
     n, w = hits.shape
     d = np.asarray(ray_dir, F32)
-    x = np.broadcast_to(np.arange(w, dtype=F32)[None, :], (n, w))
+    x = np.broadcast_to((x_begin + np.arange(w)).astype(F32)[None, :], (n, w))
     y = np.broadcast_to((row_begin + np.arange(n)).astype(F32)[:, None], (n, w))
     t = hits["t"]
     with np.errstate(all="ignore"):
         return x + t * d[0], y + t * d[1], F32(0.0) + t * d[2]
 
 
-def surfaces_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR):
-    """(rows x w) surface records of a hit frame band starting at row_begin."""
+def surfaces_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR, x_begin=0, flipped=None):
+    """(rows x w) surface records of a hit frame band starting at row_begin
+    (and at column x_begin of its frame).  `flipped`: a (rows x w) bool array
+    that receives where the facing step negated the normal."""
     n, w = hits.shape
     d = np.ascontiguousarray(ray_dir, F32)
     t, obj = hits["t"], hits["object"]
     nc = scene.num_cubes
     nx, ny, nz = (np.zeros((n, w), F32) for _ in range(3))
     tri = np.full((n, w), -1, np.int32)
-    px, py, pz = hit_points(hits, row_begin, d)
+    px, py, pz = hit_points(hits, row_begin, d, x_begin)
     cubes = np.ascontiguousarray(scene.cube_vertices, F32).reshape(-1, 36, 4)
     with np.errstate(all="ignore"):
         for c in np.unique(obj[(obj >= 0) & (obj < nc)]):
@@ -101,7 +105,7 @@ def surfaces_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR):
             for k in range(12):
                 v0, v1, v2 = cubes[c, 3 * k, :3], cubes[c, 3 * k + 1, :3], cubes[c, 3 * k + 2, :3]
                 td = oracle.tri_t_grid(cubes[c, 3 * k], cubes[c, 3 * k + 1], cubes[c, 3 * k + 2],
-                                       d, 0, row_begin, w, n)
+                                       d, x_begin, row_begin, w, n)
                 match = todo & ~np.isnan(td) & (td.astype(F32) == t)
                 if not match.any():
                     continue
@@ -118,20 +122,24 @@ def surfaces_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR):
         s = (nx * d[0] + ny * d[1]) + nz * d[2]
         flip = s > 0
         nx[flip], ny[flip], nz[flip] = -nx[flip], -ny[flip], -nz[flip]
+        if flipped is not None:
+            flipped[...] = flip
     out = np.empty((n, w), surface_dtype())
     out["nx"], out["ny"], out["nz"], out["triangle"] = nx, ny, nz, tri
     return out
 
 
-def light_factor_ref(scene, hits, surf, row_begin=0, ray_dir=REF_DIR):
+def light_factor_ref(scene, hits, surf, row_begin=0, ray_dir=REF_DIR, x_begin=0, terms=None):
     """k per pixel: 1 without lights or without an object, else the clamped
-    sum of the positive cosines."""
+    sum of the positive cosines.  `terms`: a dict that receives "ll" and "c"
+    (lights x rows x w) and "sum" (the sum before the clamp)."""
     n, w = hits.shape
     lights = np.ascontiguousarray(scene.lights, F32).reshape(-1, 4)
     k = np.ones((n, w), F32)
     if len(lights) == 0:
         return k
-    px, py, pz = hit_points(hits, row_begin, ray_dir)
+    px, py, pz = hit_points(hits, row_begin, ray_dir, x_begin)
+    lls, cs = [], []
     acc = np.zeros((n, w), F32)
     with np.errstate(all="ignore"):
         for l in lights:
@@ -139,6 +147,11 @@ def light_factor_ref(scene, hits, surf, row_begin=0, ray_dir=REF_DIR):
             ll = np.sqrt((lx * lx + ly * ly) + lz * lz)
             c = ((surf["nx"] * lx + surf["ny"] * ly) + surf["nz"] * lz) / ll
             acc = np.where(c > 0, acc + c, acc)
+            if terms is not None:
+                lls.append(ll)
+                cs.append(c)
+        if terms is not None:
+            terms.update(ll=np.array(lls), c=np.array(cs), sum=acc)
         acc = np.where(acc > 1, F32(1.0), acc)
     return np.where(hits["object"] == -1, F32(1.0), acc).astype(F32)
 
@@ -150,11 +163,13 @@ def x86_int(v):
         return np.where(ok, np.where(ok, v, F32(0.0)).astype(np.int64), INT_MIN).astype(np.int32)
 
 
-def lit_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR, surf=None):
-    """The int32x4 frame of rt_light_hits (pack with oracle.pack_rgba8)."""
+def lit_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR, surf=None, x_begin=0, k=None):
+    """The int32x4 frame of rt_light_hits (pack with oracle.pack_rgba8).
+    `k`: light_factor_ref's result where the caller already has it."""
     if surf is None:
-        surf = surfaces_ref(oracle, scene, hits, row_begin, ray_dir)
-    k = light_factor_ref(scene, hits, surf, row_begin, ray_dir)
+        surf = surfaces_ref(oracle, scene, hits, row_begin, ray_dir, x_begin)
+    if k is None:
+        k = light_factor_ref(scene, hits, surf, row_begin, ray_dir, x_begin)
     t, obj = hits["t"], hits["object"]
     table = np.concatenate([np.ascontiguousarray(scene.cube_colours, F32).reshape(-1, 4),
                             np.ascontiguousarray(scene.sphere_colours, F32).reshape(-1, 4),

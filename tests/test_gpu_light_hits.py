@@ -3,7 +3,8 @@
 tests/test_light_hits.py pins to the numpy restatement and the oracle.
 
 Device memory is torch tensors.  Every output sits inside a larger tensor
-pre-filled with a pattern, and the words around it must come back unchanged.
+pre-filled with a pattern, and the words around it must come back unchanged
+(the harness of tests/light_device.py, shared with test_gpu_light_edges.py).
 Frames are compared as raw 32-bit words.
 """
 import numpy as np
@@ -12,67 +13,11 @@ import pytest
 import light_ref as lr
 from gpu_support import H, SCENE_ARRAYS, W, base_scene, device_scene
 from hit_ref import K_FAR, REF_DIR, distinct_colours
+from light_device import PATTERN, compare_all, run_device, unguard, upload_hits
 from light_ref import ONE_LIGHT, THREE_LIGHTS, edge_scenes, eq
 
 gpu = pytest.mark.gpu
 F32 = np.float32
-PATTERN = 0x5A5A5A5A
-GUARD = 64  # int32 words in front of and behind every device output (256 B)
-WORDS = {"surface": 4, "i32x4": 4, "rgba8": 1}
-
-
-def run_device(pkg, rt, torch, ds, hits_dev, w, rows, what, d=REF_DIR, stream=None):
-    """One device call into a guarded tensor; returns the tensor.  `rows`:
-    (row_begin, row_end).  Asynchronous when `stream` is given."""
-    n = (rows[1] - rows[0]) * w
-    buf = torch.full((2 * GUARD + n * WORDS[what],), PATTERN, dtype=torch.int32, device="cuda:0")
-    out_ptr = buf.data_ptr() + 4 * GUARD
-    assert out_ptr % 16 == 0 and hits_dev.data_ptr() % 8 == 0
-    st = stream or 0  # 0: the context's own stream, which does not wait for torch's
-    if not st:
-        torch.cuda.synchronize()  # the fill above and the caller's uploads are done
-    if what == "surface":
-        rt.hit_surfaces_device(hits_dev.data_ptr(), ds, w, rows, out_ptr, ray_dir=d, stream=st)
-    else:
-        rt.light_hits_device(hits_dev.data_ptr(), ds, w, rows, out_ptr, ray_dir=d, stream=st,
-                             fmt=what)
-    return buf
-
-
-def unguard(torch, pkg, buf, w, rows, what):
-    """The host copy of a run_device tensor, guards checked and removed."""
-    torch.cuda.synchronize()  # every stream, the context's own included
-    a = buf.cpu().numpy().view(np.uint32)
-    assert (a[:GUARD] == PATTERN).all() and (a[-GUARD:] == PATTERN).all(), "wrote out of bounds"
-    body, n = a[GUARD:-GUARD], rows[1] - rows[0]
-    if what == "surface":
-        return body.view(pkg.SURFACE_DTYPE).reshape(n, w)
-    return body.view(np.int32).reshape(n, w, 4) if what == "i32x4" else body.reshape(n, w)
-
-
-def upload_hits(torch, hits):
-    return torch.from_numpy(np.array(hits).view(np.int32).reshape(hits.shape + (2,))).to("cuda:0")
-
-
-def host_result(pkg, hits, scene, rows, what, d=REF_DIR):
-    if what == "surface":
-        return pkg.hit_surfaces(hits, scene, rows=rows, ray_dir=d)
-    return pkg.light_hits(hits, scene, what, rows=rows, ray_dir=d)
-
-
-def compare_all(pkg, rt, torch, scene, hits, w, rows, d=REF_DIR, label=""):
-    """Surfaces and both lit formats of `hits` on the device against the host."""
-    ds, keep = device_scene(torch, scene)
-    hd = upload_hits(torch, hits)
-    out = {}
-    for what in ("surface", "i32x4", "rgba8"):
-        buf = run_device(pkg, rt, torch, ds, hd, w, rows, what, d)
-        got = unguard(torch, pkg, buf, w, rows, what)
-        want = host_result(pkg, hits, scene, rows, what, d)
-        assert not eq(got, want), f"{label} {what}: {eq(got, want)}"
-        out[what] = got
-    del keep
-    return out
 
 
 # --- 1. the base scene: surfaces, 0 / 1 / 3 lights, both formats ----------------
