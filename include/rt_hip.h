@@ -382,6 +382,41 @@ int rt_light_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene*
                          const float ray_dir[4], int32_t width, int32_t row_begin,
                          int32_t row_end, int32_t out_format, void* device_out, void* stream);
 
+/* ---- hard shadows for the light pass ----------------- */
+/* For each hit pixel and each light that faces it (the cosine c of
+ * rt_light_hits is > 0), an any-hit test of the segment from the hit point
+ * to the light against every other object of the scene: all twelve
+ * triangles of every other cube (the reference's fp64 test, strictly between
+ * the hit point and the light) and every other sphere (fp32).  The pixel's
+ * own object is never an occluder: cubes and spheres are convex, so no bias
+ * constant exists and none is needed.
+ *
+ * rt_shadow_hits*: one uint32 per pixel; bit i is set iff light i faces the
+ * pixel and is occluded.  Misses give 0.  RT_ERR_UNSUPPORTED for more than
+ * 32 lights (these two calls only).
+ * rt_light_hits_shadowed*: rt_light_hits* with the occluded lights left out
+ * of the sum k; any number of lights.  With num_lights == 0 it is
+ * rt_shade_hits' frame; a lit pixel whose lights are all occluded is
+ * (0, 0, 0, 255).
+ *
+ * Arguments, alignment (the mask: 4 bytes), the 2^39-pixel launch limit, the
+ * handling of `object` (the host functions refuse an id outside
+ * [-1, num_cubes + num_spheres), the kernel treats it as -1) and asynchrony
+ * are those of rt_light_hits / rt_light_hits_device.  Host and device
+ * results are bit-identical. */
+int rt_shadow_hits(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                   int32_t width, int32_t row_begin, int32_t row_end, uint32_t* out);
+int rt_light_hits_shadowed(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                           int32_t width, int32_t row_begin, int32_t row_end,
+                           int32_t out_format, void* out);
+int rt_shadow_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
+                          const float ray_dir[4], int32_t width, int32_t row_begin,
+                          int32_t row_end, uint32_t* device_out, void* stream);
+int rt_light_hits_shadowed_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                  const rt_scene* device_scene, const float ray_dir[4],
+                                  int32_t width, int32_t row_begin, int32_t row_end,
+                                  int32_t out_format, void* device_out, void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

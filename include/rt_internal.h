@@ -1,6 +1,6 @@
 /*
  * rt_internal.h -- shared between the library's own translation units
- * (rt_device.hip, rt_scene_device.hip, rt_light.hip).  Not installed, not part of the ABI.
+ * (rt_device.hip, rt_scene_device.hip, rt_light.hip, rt_shadow.hip).  Not installed, not part of the ABI.
  */
 #ifndef RT_INTERNAL_H
 #define RT_INTERNAL_H
@@ -18,6 +18,8 @@ hipStream_t ctx_stream(rt_ctx* ctx);
 int preload_scene_kernels();
 // the same for rt_light.hip's kernels
 int preload_light_kernels();
+// ... and rt_shadow.hip's
+int preload_shadow_kernels();
 }  // namespace rt_internal
 
 #endif /* RT_INTERNAL_H */

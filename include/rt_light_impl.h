@@ -1,8 +1,9 @@
 /*
  * rt_light_impl.h -- the per-pixel arithmetic of rt_hit_surfaces* and
- * rt_light_hits* (DESIGN.md §3.1a), one text for the host functions
- * (csrc/rt_light.cpp) and the kernel (csrc/rt_light.hip), and their shared
- * argument check.  Internal: not installed, not part of the ABI.
+ * rt_light_hits*  and of the shadow term, rt_shadow_hits*
+ * and rt_light_hits_shadowed* (§3.1b): one text for the host functions
+ * (csrc/rt_light.cpp) and the kernels (csrc/rt_light.hip, csrc/rt_shadow.hip),
+ * and their shared argument check.  Internal: not installed, not part of the ABI.
  *
  * Every fp32 operation is written on its own and rounds once; both builds
  * use -ffp-contract=off, the device's '/' and sqrtf are IEEE
@@ -196,6 +197,122 @@ RT_LIGHT_FN void lit_pixel(const rt_scene& s, int32_t obj, const float* verts, f
         k = light_factor(Vec3{n.nx, n.ny, n.nz}, p, s.lights, s.num_lights);
     }
     shade_lit(t, k, colour, out);
+}
+
+/* ---- the shadow term ------------------------------------
+ * For a hit pixel and a light that faces it (c > 0): is the segment from the
+ * hit point p to the light, p + s * L with s in (0, 1), cut by any object
+ * other than the pixel's own?
+ *
+ * The pixel's own object is never an occluder, and that is exact, not a
+ * bias: cubes and spheres are convex, and a point of a convex surface that
+ * faces the light sees it without entering its own object again.  A scene
+ * with a non-convex primitive would need its own object tested too.
+ *
+ * "Any" does not depend on the order of the tests, so the callers may test
+ * in any order and stop at the first occluder. */
+
+// One triangle (three float4 at `tri`): the fp64 test on p and the
+// un-normalised L as doubles, strictly between the hit point and the light
+// (the light sits at parameter 1).
+RT_LIGHT_FN bool occluded_by_tri(const double* p, const double* L, const float* tri) {
+    const double v0[3] = {tri[0], tri[1], tri[2]}, v1[3] = {tri[4], tri[5], tri[6]},
+                 v2[3] = {tri[8], tri[9], tri[10]};
+    double td;
+    return intersect_tri(p, L, v0, v1, v2, &td) == 1 && td > 0.0 && td < 1.0;
+}
+
+// One sphere (float4 centre, radius r), all fp32: the roots of
+// a*s*s - 2*b*s + q = 0.  Non-finite values compare false: not occluded.
+RT_LIGHT_FN bool occluded_by_sphere(Vec3 p, Vec3 L, const float* centre, float r) {
+    const Vec3 m{centre[0] - p.x, centre[1] - p.y, centre[2] - p.z};
+    const float a = (L.x * L.x + L.y * L.y) + L.z * L.z;
+    const float b = (m.x * L.x + m.y * L.y) + m.z * L.z;
+    const float q = ((m.x * m.x + m.y * m.y) + m.z * m.z) - r * r;
+    const float disc = b * b - a * q;
+    if (!(disc >= 0.0f)) return false;
+    const float sq = sqrtf(disc);
+    const float s0 = (b - sq) / a;
+    const float s1 = (b + sq) / a;
+    return (s0 > 0.0f && s0 < 1.0f) || (s1 > 0.0f && s1 < 1.0f);
+}
+
+// Does any object but `obj` (range-checked: a colour slot of `s`) occlude
+// the light at p + L?  The loops index 0 .. count-1 only; `obj` is compared.
+RT_LIGHT_FN bool light_occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L) {
+    const double pd[3] = {p.x, p.y, p.z};
+    const double Ld[3] = {L.x, L.y, L.z};
+    for (int32_t j = 0; j < s.num_cubes; ++j) {
+        if (j == obj) continue;
+        const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
+        for (int k = 0; k < 12; ++k)
+            if (occluded_by_tri(pd, Ld, v + 12 * k)) return true;
+    }
+    for (int32_t i = 0; i < s.num_spheres; ++i) {
+        if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
+        if (occluded_by_sphere(p, L, s.sphere_origins + 4 * static_cast<int64_t>(i),
+                               s.sphere_radius[i]))
+            return true;
+    }
+    return false;
+}
+
+// Bit i: light i faces the pixel (c > 0) and is occluded.  At most 32 lights
+// (the callers refuse more); n is the faced normal of a hit pixel.
+RT_LIGHT_FN uint32_t shadow_mask(const rt_scene& s, int32_t obj, Vec3 n, Vec3 p) {
+    uint32_t mask = 0;
+    for (int32_t i = 0; i < s.num_lights && i < 32; ++i) {
+        const float* l = s.lights + 4 * static_cast<int64_t>(i);
+        const Vec3 L{l[0] - p.x, l[1] - p.y, l[2] - p.z};
+        const float ll = sqrtf((L.x * L.x + L.y * L.y) + L.z * L.z);
+        const float c = ((n.x * L.x + n.y * L.y) + n.z * L.z) / ll;
+        if (c > 0.0f && light_occluded(s, obj, p, L)) mask |= 1u << i;
+    }
+    return mask;
+}
+
+// light_factor with the occluded lights left out of the sum.
+RT_LIGHT_FN float shadowed_factor(const rt_scene& s, int32_t obj, Vec3 n, Vec3 p) {
+    float k = 0.0f;
+    for (int32_t i = 0; i < s.num_lights; ++i) {
+        const float* l = s.lights + 4 * static_cast<int64_t>(i);
+        const Vec3 L{l[0] - p.x, l[1] - p.y, l[2] - p.z};
+        const float ll = sqrtf((L.x * L.x + L.y * L.y) + L.z * L.z);
+        const float c = ((n.x * L.x + n.y * L.y) + n.z * L.z) / ll;
+        if (c > 0.0f && !light_occluded(s, obj, p, L)) k = k + c;
+    }
+    if (k > 1.0f) k = 1.0f;
+    return k;
+}
+
+// The colour of slot `obj` ((0, 0, 0) for -1), as lit_pixel reads it.
+RT_LIGHT_FN Vec3 slot_colour(const rt_scene& s, int32_t obj) {
+    if (obj < 0) return Vec3{0.0f, 0.0f, 0.0f};
+    const float* c = obj < s.num_cubes
+                         ? s.cube_colours + 4 * static_cast<int64_t>(obj)
+                         : s.sphere_colours + 4 * static_cast<int64_t>(obj - s.num_cubes);
+    return Vec3{c[0], c[1], c[2]};
+}
+
+// lit_pixel with shadowed_factor in place of light_factor.
+RT_LIGHT_FN void lit_pixel_shadowed(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                                    float oy, Vec3 d, float t, int32_t out[4]) {
+    float k = 1.0f;
+    if (s.num_lights > 0 && obj >= 0) {
+        const Vec3 p = hit_point(ox, oy, d, t);
+        const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
+        k = shadowed_factor(s, obj, Vec3{n.nx, n.ny, n.nz}, p);
+    }
+    shade_lit(t, k, slot_colour(s, obj), out);
+}
+
+// The mask of one pixel (0 for a miss or without lights).
+RT_LIGHT_FN uint32_t shadow_pixel(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                                  float oy, Vec3 d, float t) {
+    if (s.num_lights <= 0 || obj < 0) return 0;
+    const Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
+    return shadow_mask(s, obj, Vec3{n.nx, n.ny, n.nz}, p);
 }
 
 }  // namespace rt_light

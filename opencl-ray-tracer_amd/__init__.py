@@ -26,7 +26,7 @@ __all__ = [
     "library", "library_path", "primary_ray_dir", "pack_rgba8", "cube_packed",
     "deg_to_rad", "encode_png", "EXPORTED_SYMBOLS", "CUBE_OP_DTYPE", "cube_ops", "render_multi",
     "debug_glibc_sincosf", "host_register", "host_unregister", "HIT_DTYPE", "HIT_MISS_T",
-    "shade_hits", "SURFACE_DTYPE", "hit_surfaces", "light_hits",
+    "shade_hits", "SURFACE_DTYPE", "hit_surfaces", "light_hits", "shadow_hits",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -56,7 +56,8 @@ EXPORTED_SYMBOLS = (
     "rt_render_multi", "rt_shared_alloc", "rt_shared_open", "rt_shared_close", "rt_shared_free",
     "rt_host_register", "rt_host_unregister", "rt_reserve", "rt_last_kernel", "rt_fnv1a64",
     "rt_shade_hits", "rt_hit_surfaces", "rt_light_hits", "rt_hit_surfaces_device",
-    "rt_light_hits_device",
+    "rt_light_hits_device", "rt_shadow_hits", "rt_light_hits_shadowed", "rt_shadow_hits_device",
+    "rt_light_hits_shadowed_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -169,6 +170,13 @@ def library() -> ctypes.CDLL:
                                                   i32, vp, vp]),
         "rt_light_hits_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32, i32,
                                                 i32, i32, vp, vp]),
+        "rt_shadow_hits": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32, vp]),
+        "rt_light_hits_shadowed": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32,
+                                                  i32, vp]),
+        "rt_shadow_hits_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32, i32,
+                                                 i32, vp, vp]),
+        "rt_light_hits_shadowed_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32,
+                                                         i32, i32, i32, vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -457,18 +465,36 @@ def hit_surfaces(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]]
 
 def light_hits(hits: np.ndarray, scene: Scene, fmt: str = "i32x4",
                rows: Optional[Tuple[int, int]] = None,
-               ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+               ray_dir: Optional[np.ndarray] = None, shadows: bool = False) -> np.ndarray:
     """rt_light_hits: shade_hits with the depth ramp scaled by the diffuse
     term of `scene.lights` (see include/rt_hip.h); without lights it is
-    shade_hits' frame bit for bit.  On the host."""
+    shade_hits' frame bit for bit.  shadows=True (rt_light_hits_shadowed):
+    a light that another object of the scene hides from the hit point adds
+    nothing.  On the host."""
     if fmt not in ("i32x4", "rgba8"):
         raise ValueError("light_hits gives an i32x4 or an rgba8 frame")
     hits, rb, re = _hit_band(hits, rows)
     d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
     out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
     sc = scene.as_c()
-    _check(library().rt_light_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
-                                   _FORMATS[fmt], _ptr(out)), "rt_light_hits")
+    fn, name = ((library().rt_light_hits_shadowed, "rt_light_hits_shadowed") if shadows
+                else (library().rt_light_hits, "rt_light_hits"))
+    _check(fn(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re, _FORMATS[fmt],
+              _ptr(out)), name)
+    return out
+
+
+def shadow_hits(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
+                ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_shadow_hits: per pixel of a "hit" frame a uint32 whose bit i is set
+    iff light i of `scene.lights` faces the hit point and another object of
+    the scene hides it (at most 32 lights).  On the host."""
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(hits.shape, np.uint32)
+    sc = scene.as_c()
+    _check(library().rt_shadow_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
+                                    _ptr(out)), "rt_shadow_hits")
     return out
 
 
@@ -580,19 +606,31 @@ class RayTracer:
     def light_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
                           rows: Tuple[int, int], out_ptr: int,
                           ray_dir: Optional[np.ndarray] = None, stream: int = 0,
-                          fmt: str = "i32x4") -> None:
+                          fmt: str = "i32x4", shadows: bool = False) -> None:
         """rt_light_hits_device: a device hit frame to a lit "i32x4" or "rgba8"
         frame at `out_ptr`, with the lights of `device_scene` (optional keys
         "lights": device address of float4[num_lights], "num_lights").
-        Asynchronous on `stream`."""
+        shadows=True: rt_light_hits_shadowed_device.  Asynchronous on `stream`."""
         if fmt not in ("i32x4", "rgba8"):
             raise ValueError("light_hits_device gives an i32x4 or an rgba8 frame")
         d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
         sc = _device_scene(device_scene)
-        _check(library().rt_light_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
-                                              _ptr(d), width, rows[0], rows[1], _FORMATS[fmt],
-                                              out_ptr or None, stream or None),
-               "rt_light_hits_device")
+        fn, name = ((library().rt_light_hits_shadowed_device, "rt_light_hits_shadowed_device")
+                    if shadows else (library().rt_light_hits_device, "rt_light_hits_device"))
+        _check(fn(self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
+                  _FORMATS[fmt], out_ptr or None, stream or None), name)
+
+    def shadow_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
+                           rows: Tuple[int, int], out_ptr: int,
+                           ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
+        """rt_shadow_hits_device: a device hit frame to one uint32 shadow mask
+        per pixel at `out_ptr` (at most 32 lights).  Asynchronous on `stream`."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_shadow_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
+                                               _ptr(d), width, rows[0], rows[1],
+                                               out_ptr or None, stream or None),
+               "rt_shadow_hits_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,
