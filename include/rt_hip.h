@@ -417,6 +417,49 @@ int rt_light_hits_shadowed_device(rt_ctx* ctx, const rt_hit* device_hits,
                                   int32_t width, int32_t row_begin, int32_t row_end,
                                   int32_t out_format, void* device_out, void* stream);
 
+/* ---- mirror reflections for the light pass ------------ */
+/* For each hit pixel, the closest hit of the ray that leaves the hit point p
+ * along the mirrored direction R = d - 2 (n . d) n (n: the faced unit normal
+ * of rt_hit_surfaces; R is not normalised), over every other object of the
+ * scene: all twelve triangles of every other cube (the reference's fp64 test
+ * on p and R, t > 0) and every other sphere (fp32; the far root where p lies
+ * inside it).  Cubes first, then spheres, each in slot order; a candidate
+ * wins iff it is strictly nearer, so ties go to the first.  The pixel's own
+ * object is never a candidate: cubes and spheres are convex and the mirrored
+ * ray leaves its surface, so no bias constant exists and none is needed.
+ * Renders cast no secondary rays; this is a post-pass over a hit frame.
+ *
+ * rt_reflect_hits*: one rt_hit per pixel, the bounce: the parameter along R
+ * and the colour slot met.  (300000, -1) where the bounce meets nothing, for
+ * a primary miss, and for a pixel whose normal is NaN.
+ * rt_light_hits_reflected*: rt_light_hits* (no shadows) blended with what
+ * each pixel mirrors: per channel a + reflectivity * (b - a), a the pixel's
+ * own lit channel and b the lit channel of the bounce's hit point, whose
+ * depth ramp runs over t + the bounce's parameter and is clamped at 0 from
+ * below (0 where the bounce misses).  reflectivity == 0 gives rt_light_hits'
+ * frame word for word, without a walk; misses and pixels with t == 300000
+ * are rt_light_hits' pixels for every reflectivity.
+ *
+ * RT_ERR_INVALID_ARG for a reflectivity outside [0, 1] or NaN.  Arguments,
+ * alignment (the bounce frame: 8 bytes), the 2^39-pixel launch limit, the
+ * handling of `object` (the host functions refuse an id outside
+ * [-1, num_cubes + num_spheres), the kernel treats it as -1) and asynchrony
+ * are those of rt_light_hits / rt_light_hits_device.  Host and device
+ * results are bit-identical. */
+int rt_reflect_hits(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                    int32_t width, int32_t row_begin, int32_t row_end, rt_hit* out);
+int rt_light_hits_reflected(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                            int32_t width, int32_t row_begin, int32_t row_end,
+                            float reflectivity, int32_t out_format, void* out);
+int rt_reflect_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
+                           const float ray_dir[4], int32_t width, int32_t row_begin,
+                           int32_t row_end, rt_hit* device_out, void* stream);
+int rt_light_hits_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                   const rt_scene* device_scene, const float ray_dir[4],
+                                   int32_t width, int32_t row_begin, int32_t row_end,
+                                   float reflectivity, int32_t out_format, void* device_out,
+                                   void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

@@ -1,6 +1,7 @@
 /*
  * rt_internal.h -- shared between the library's own translation units
- * (rt_device.hip, rt_scene_device.hip, rt_light.hip, rt_shadow.hip).  Not installed, not part of the ABI.
+ * (rt_device.hip, rt_scene_device.hip, rt_light.hip, rt_shadow.hip,
+ * rt_reflect.hip).  Not installed, not part of the ABI.
  */
 #ifndef RT_INTERNAL_H
 #define RT_INTERNAL_H
@@ -20,6 +21,8 @@ int preload_scene_kernels();
 int preload_light_kernels();
 // ... and rt_shadow.hip's
 int preload_shadow_kernels();
+// ... and rt_reflect.hip's
+int preload_reflect_kernels();
 }  // namespace rt_internal
 
 #endif /* RT_INTERNAL_H */

@@ -1,9 +1,11 @@
 /*
  * rt_light_impl.h -- the per-pixel arithmetic of rt_hit_surfaces* and
- * rt_light_hits*  and of the shadow term, rt_shadow_hits*
- * and rt_light_hits_shadowed* (§3.1b): one text for the host functions
- * (csrc/rt_light.cpp) and the kernels (csrc/rt_light.hip, csrc/rt_shadow.hip),
- * and their shared argument check.  Internal: not installed, not part of the ABI.
+ * rt_light_hits* (DESIGN.md §3.1a), of the shadow term, rt_shadow_hits*
+ * and rt_light_hits_shadowed* (§3.1b), and of the mirror bounce,
+ * rt_reflect_hits* and rt_light_hits_reflected* (§3.1c): one text for the host
+ * functions (csrc/rt_light.cpp) and the kernels (csrc/rt_light.hip,
+ * csrc/rt_shadow.hip, csrc/rt_reflect.hip), and their shared argument check.
+ * Internal: not installed, not part of the ABI.
  *
  * Every fp32 operation is written on its own and rounds once; both builds
  * use -ffp-contract=off, the device's '/' and sqrtf are IEEE
@@ -25,7 +27,7 @@
 
 namespace rt_light {
 
-/* The common checks of the four entry points (0 or RT_ERR_INVALID_ARG):
+/* The common checks of the entry points (0 or RT_ERR_INVALID_ARG):
  * NULL pointers, width / rows (the pixel-coordinate limits of
  * rt_args::check_args), counts, and arrays missing for a non-zero count,
  * lights included.  csrc/rt_light.cpp. */
@@ -313,6 +315,163 @@ RT_LIGHT_FN uint32_t shadow_pixel(const rt_scene& s, int32_t obj, const float* v
     const Vec3 p = hit_point(ox, oy, d, t);
     const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
     return shadow_mask(s, obj, Vec3{n.nx, n.ny, n.nz}, p);
+}
+
+/* ---- the mirror bounce -----------------------------------
+ * For a hit pixel: the closest hit of the ray that leaves the hit point p
+ * along the mirrored direction R, over every object but the pixel's own.
+ *
+ * Leaving the own object out is exact for the reason given above for the
+ * shadow term: cubes and spheres are convex and n . R = -(n . d) >= 0 for the
+ * faced normal, so the mirrored ray leaves its own surface and cannot enter
+ * its own object again.  A non-convex primitive would need its own object
+ * tested too. */
+
+// d mirrored at the faced unit normal n; not normalised.  n = 0 gives d.
+RT_LIGHT_FN Vec3 mirror_dir(Vec3 n, Vec3 d) {
+    const float s = (n.x * d.x + n.y * d.y) + n.z * d.z;
+    const float f = s + s;
+    return Vec3{d.x - f * n.x, d.y - f * n.y, d.z - f * n.z};
+}
+
+// One triangle (three float4 at `tri`): the fp64 test on p and R as doubles.
+// A candidate iff it returns 1 with td > 0; its parameter is (float)td.
+RT_LIGHT_FN bool bounce_tri(const double* p, const double* R, const float* tri, float* sf) {
+    const double v0[3] = {tri[0], tri[1], tri[2]}, v1[3] = {tri[4], tri[5], tri[6]},
+                 v2[3] = {tri[8], tri[9], tri[10]};
+    double td;
+    if (intersect_tri(p, R, v0, v1, v2, &td) != 1 || !(td > 0.0)) return false;
+    *sf = static_cast<float>(td);
+    return true;
+}
+
+// One sphere: the quadratic of occluded_by_sphere with R in place of L.  The
+// near root where it is ahead of p, else the far one (p inside the sphere).
+RT_LIGHT_FN bool bounce_sphere(Vec3 p, Vec3 R, const float* centre, float r, float* sf) {
+    const Vec3 m{centre[0] - p.x, centre[1] - p.y, centre[2] - p.z};
+    const float a = (R.x * R.x + R.y * R.y) + R.z * R.z;
+    const float b = (m.x * R.x + m.y * R.y) + m.z * R.z;
+    const float q = ((m.x * m.x + m.y * m.y) + m.z * m.z) - r * r;
+    const float disc = b * b - a * q;
+    if (!(disc >= 0.0f)) return false;
+    const float sq = sqrtf(disc);
+    const float s0 = (b - sq) / a;
+    const float s1 = (b + sq) / a;
+    if (s0 > 0.0f) {
+        *sf = s0;
+        return true;
+    }
+    if (s1 > 0.0f) {
+        *sf = s1;
+        return true;
+    }
+    return false;
+}
+
+// The closest hit of a bounce: its parameter along R (kFar: nothing), the
+// colour slot and, for a cube, the triangle.
+struct Bounce {
+    float best;
+    int32_t obj2, tri2;
+};
+
+// The walk from p along R over every object but `obj` (range-checked: a
+// colour slot of `s`; compared, never an index): cubes 0 .. nc-1 with
+// triangles 0 .. 11, then spheres 0 .. ns-1.  A candidate is taken iff
+// sf < best, so ties go to the first in that order (the reference's rule).
+RT_LIGHT_FN Bounce bounce_walk(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R) {
+    Bounce b{kFar, -1, -1};
+    const double pd[3] = {p.x, p.y, p.z};
+    const double Rd[3] = {R.x, R.y, R.z};
+    float sf;
+    for (int32_t j = 0; j < s.num_cubes; ++j) {
+        if (j == obj) continue;
+        const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
+        for (int k = 0; k < 12; ++k)
+            if (bounce_tri(pd, Rd, v + 12 * k, &sf) && sf < b.best) b = Bounce{sf, j, k};
+    }
+    for (int32_t i = 0; i < s.num_spheres; ++i) {
+        if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
+        if (bounce_sphere(p, R, s.sphere_origins + 4 * static_cast<int64_t>(i),
+                          s.sphere_radius[i], &sf) &&
+            sf < b.best)
+            b = Bounce{sf, s.num_cubes + i, -1};
+    }
+    return b;
+}
+
+// The unit normal at the bounce's hit point p2, turned against R.  `obj2` is
+// a colour slot of `s` and `tri2` a triangle of that cube (bounce_walk's).
+RT_LIGHT_FN Vec3 bounce_normal(const rt_scene& s, int32_t obj2, int32_t tri2, Vec3 p2, Vec3 R) {
+    Vec3 n;
+    if (obj2 < s.num_cubes) {
+        const float* a = s.cube_vertices + 144 * static_cast<int64_t>(obj2) + 12 * tri2;
+        const float* b = a + 4;
+        const float* c = a + 8;
+        const Vec3 e1{b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+        const Vec3 e2{c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+        n = normalise(Vec3{e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z,
+                           e1.x * e2.y - e1.y * e2.x});
+    } else {
+        const float* c = s.sphere_origins + 4 * static_cast<int64_t>(obj2 - s.num_cubes);
+        n = normalise(Vec3{p2.x - c[0], p2.y - c[1], p2.z - c[2]});
+    }
+    return face(n, R);
+}
+
+// The mirrored pixel after the walk: the unshadowed lit pixel (ramp of t
+// scaled by k, as shade_lit) blended by r with what the bounce `b` met.  For
+// a hit pixel with t != kFar.
+RT_LIGHT_FN void shade_mirrored(const rt_scene& s, int32_t obj, float t, float k, Vec3 p, Vec3 R,
+                                Bounce b, float r, int32_t out[4]) {
+    const float normalised = (t - 0.0f) / (180.0f - 0.0f);
+    const float scalar = 255.0f - (normalised * 255.0f);
+    const float lit = scalar * k;
+    const Vec3 colour = slot_colour(s, obj);
+    float lit2 = 0.0f;
+    Vec3 colour2{0.0f, 0.0f, 0.0f};
+    if (b.obj2 >= 0) {
+        const Vec3 p2{p.x + b.best * R.x, p.y + b.best * R.y, p.z + b.best * R.z};
+        float k2 = 1.0f;
+        if (s.num_lights > 0)
+            k2 = light_factor(bounce_normal(s, b.obj2, b.tri2, p2, R), p2, s.lights, s.num_lights);
+        const float t2 = t + b.best;
+        const float normalised2 = (t2 - 0.0f) / (180.0f - 0.0f);
+        float scalar2 = 255.0f - (normalised2 * 255.0f);
+        // beyond the ramp's end a mirrored object adds nothing, not negative light
+        if (!(scalar2 > 0.0f)) scalar2 = 0.0f;
+        lit2 = scalar2 * k2;
+        colour2 = slot_colour(s, b.obj2);
+    }
+    const float a[3] = {lit * colour.x, lit * colour.y, lit * colour.z};
+    const float m[3] = {lit2 * colour2.x, lit2 * colour2.y, lit2 * colour2.z};
+    for (int c = 0; c < 3; ++c) out[c] = cvt_i32(a[c] + r * (m[c] - a[c]));
+    out[3] = 255;
+}
+
+// The bounce of one pixel ((kFar, -1) for a miss).  `obj`, `verts` as for surface().
+RT_LIGHT_FN Bounce bounce_pixel(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                                float oy, Vec3 d, float t) {
+    if (obj < 0) return Bounce{kFar, -1, -1};
+    const Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
+    return bounce_walk(s, obj, p, mirror_dir(Vec3{n.nx, n.ny, n.nz}, d));
+}
+
+// One mirrored lit pixel (int32x4), r != 0.  A miss, and t == kFar, are lit_pixel's.
+RT_LIGHT_FN void lit_pixel_reflected(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                                     float oy, Vec3 d, float t, float r, int32_t out[4]) {
+    if (obj < 0 || t == kFar) {
+        lit_pixel(s, obj, verts, ox, oy, d, t, out);
+        return;
+    }
+    const Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
+    const Vec3 n{sf.nx, sf.ny, sf.nz};
+    float k = 1.0f;
+    if (s.num_lights > 0) k = light_factor(n, p, s.lights, s.num_lights);
+    const Vec3 R = mirror_dir(n, d);
+    shade_mirrored(s, obj, t, k, p, R, bounce_walk(s, obj, p, R), r, out);
 }
 
 }  // namespace rt_light

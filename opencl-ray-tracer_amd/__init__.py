@@ -27,6 +27,7 @@ __all__ = [
     "deg_to_rad", "encode_png", "EXPORTED_SYMBOLS", "CUBE_OP_DTYPE", "cube_ops", "render_multi",
     "debug_glibc_sincosf", "host_register", "host_unregister", "HIT_DTYPE", "HIT_MISS_T",
     "shade_hits", "SURFACE_DTYPE", "hit_surfaces", "light_hits", "shadow_hits",
+    "reflect_hits", "light_hits_reflected",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -57,7 +58,8 @@ EXPORTED_SYMBOLS = (
     "rt_host_register", "rt_host_unregister", "rt_reserve", "rt_last_kernel", "rt_fnv1a64",
     "rt_shade_hits", "rt_hit_surfaces", "rt_light_hits", "rt_hit_surfaces_device",
     "rt_light_hits_device", "rt_shadow_hits", "rt_light_hits_shadowed", "rt_shadow_hits_device",
-    "rt_light_hits_shadowed_device",
+    "rt_light_hits_shadowed_device", "rt_reflect_hits", "rt_light_hits_reflected",
+    "rt_reflect_hits_device", "rt_light_hits_reflected_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -177,6 +179,13 @@ def library() -> ctypes.CDLL:
                                                  i32, vp, vp]),
         "rt_light_hits_shadowed_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32,
                                                          i32, i32, i32, vp, vp]),
+        "rt_reflect_hits": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32, vp]),
+        "rt_light_hits_reflected": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32,
+                                                   f32, i32, vp]),
+        "rt_reflect_hits_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32, i32,
+                                                  i32, vp, vp]),
+        "rt_light_hits_reflected_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32,
+                                                          i32, i32, f32, i32, vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -498,6 +507,41 @@ def shadow_hits(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] 
     return out
 
 
+def reflect_hits(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
+                 ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_reflect_hits: per pixel of a "hit" frame the closest hit of the ray
+    mirrored at its surface, over every other object of the scene, as a
+    HIT_DTYPE array of the same shape: the parameter along the (un-normalised)
+    mirrored direction and the colour slot; (HIT_MISS_T, -1) where the bounce
+    meets nothing or the pixel is a miss.  On the host."""
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(hits.shape, HIT_DTYPE)
+    sc = scene.as_c()
+    _check(library().rt_reflect_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
+                                     _ptr(out)), "rt_reflect_hits")
+    return out
+
+
+def light_hits_reflected(hits: np.ndarray, scene: Scene, reflectivity: float,
+                         fmt: str = "i32x4", rows: Optional[Tuple[int, int]] = None,
+                         ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_light_hits_reflected: light_hits (no shadows) with every hit pixel
+    blended by `reflectivity` in [0, 1] with the lit colour of what it
+    mirrors (black where it mirrors nothing); 0 gives light_hits' frame bit
+    for bit.  On the host."""
+    if fmt not in ("i32x4", "rgba8"):
+        raise ValueError("light_hits_reflected gives an i32x4 or an rgba8 frame")
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
+    sc = scene.as_c()
+    _check(library().rt_light_hits_reflected(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1],
+                                             rb, re, reflectivity, _FORMATS[fmt], _ptr(out)),
+           "rt_light_hits_reflected")
+    return out
+
+
 def _device_scene(device_scene: dict) -> _Scene:
     """rt_scene of device addresses, lights included (hit post-passes)."""
     g = device_scene.get
@@ -631,6 +675,34 @@ class RayTracer:
                                                _ptr(d), width, rows[0], rows[1],
                                                out_ptr or None, stream or None),
                "rt_shadow_hits_device")
+
+    def reflect_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
+                            rows: Tuple[int, int], out_ptr: int,
+                            ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
+        """rt_reflect_hits_device: a device hit frame to the hit frame of its
+        mirror bounce at `out_ptr` (8-byte aligned).  Asynchronous on `stream`."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_reflect_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
+                                                _ptr(d), width, rows[0], rows[1],
+                                                out_ptr or None, stream or None),
+               "rt_reflect_hits_device")
+
+    def light_hits_reflected_device(self, hits_ptr: int, device_scene: dict, width: int,
+                                    rows: Tuple[int, int], out_ptr: int, reflectivity: float,
+                                    ray_dir: Optional[np.ndarray] = None, stream: int = 0,
+                                    fmt: str = "i32x4") -> None:
+        """rt_light_hits_reflected_device: a device hit frame to a lit "i32x4"
+        or "rgba8" frame at `out_ptr`, every pixel blended by `reflectivity`
+        with what it mirrors.  Asynchronous on `stream`."""
+        if fmt not in ("i32x4", "rgba8"):
+            raise ValueError("light_hits_reflected_device gives an i32x4 or an rgba8 frame")
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_light_hits_reflected_device(
+            self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
+            reflectivity, _FORMATS[fmt], out_ptr or None, stream or None),
+            "rt_light_hits_reflected_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,
