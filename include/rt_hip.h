@@ -460,6 +460,59 @@ int rt_light_hits_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
                                    float reflectivity, int32_t out_format, void* device_out,
                                    void* stream);
 
+/* ---- shadows and mirror reflections together ---------- */
+/* The light pass with all three terms: the shadowed direct light of
+ * rt_light_hits_shadowed* at the hit point p, the bounce of rt_reflect_hits*,
+ * and the shadowed direct light at the point p2 the bounce meets, blended as
+ * rt_light_hits_reflected* blends.
+ *
+ * rt_light_hits_shadowed_reflected*: rt_light_hits_reflected* with the
+ * occluded lights left out of both sums: of k at p (occluders: every object
+ * but the pixel's own) and of k2 at p2 (occluders: every object but the one
+ * the bounce met).  reflectivity == 0 gives rt_light_hits_shadowed's frame
+ * word for word, without the bounce and without the second shadow walk;
+ * misses and pixels with t == 300000 are rt_light_hits_shadowed's pixels for
+ * every reflectivity; without lights it is rt_light_hits_reflected's frame.
+ * rt_shadow_hits_reflected*: one uint32 per pixel, rt_shadow_hits' mask taken
+ * at p2: bit i is set iff light i faces p2 (against the bounce's normal there,
+ * turned against R) and an object other than the one the bounce met cuts the
+ * segment from p2 to the light.  0 for a primary miss, without lights, and
+ * where the bounce meets nothing; t == 300000 is not looked at, as in
+ * rt_reflect_hits.  RT_ERR_UNSUPPORTED for more than 32 lights (these two
+ * calls only).
+ *
+ * Who is left out at p2: the object the bounce met, always, and only it.  The
+ * primary pixel's own object occludes at p2 like any other (a sphere hovering
+ * over a face shadows the point of the face that its own flank mirrors).
+ * This is exact where the bounce arrives from outside the object it met (the
+ * convexity argument of the shadow term).  It is not exact where the bounce
+ * arrives from inside it -- the far root of a sphere that holds p, or a
+ * triangle of an intersecting cube met from within: there the normal at p2 is
+ * turned inward, and the object's own far side could hide a facing light but
+ * is left out all the same.
+ *
+ * RT_ERR_INVALID_ARG for a reflectivity outside [0, 1] or NaN.  Arguments,
+ * alignment (the mask: 4 bytes), the 2^39-pixel launch limit, the handling of
+ * `object` (the host functions refuse an id outside
+ * [-1, num_cubes + num_spheres), the kernel treats it as -1) and asynchrony
+ * are those of rt_light_hits / rt_light_hits_device; one launch, no
+ * workspace.  Host and device results are bit-identical. */
+int rt_shadow_hits_reflected(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                             int32_t width, int32_t row_begin, int32_t row_end, uint32_t* out);
+int rt_light_hits_shadowed_reflected(const rt_hit* hits, const rt_scene* scene,
+                                     const float ray_dir[4], int32_t width, int32_t row_begin,
+                                     int32_t row_end, float reflectivity, int32_t out_format,
+                                     void* out);
+int rt_shadow_hits_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                    const rt_scene* device_scene, const float ray_dir[4],
+                                    int32_t width, int32_t row_begin, int32_t row_end,
+                                    uint32_t* device_out, void* stream);
+int rt_light_hits_shadowed_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                            const rt_scene* device_scene, const float ray_dir[4],
+                                            int32_t width, int32_t row_begin, int32_t row_end,
+                                            float reflectivity, int32_t out_format,
+                                            void* device_out, void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

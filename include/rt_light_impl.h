@@ -1,10 +1,12 @@
 /*
  * rt_light_impl.h -- the per-pixel arithmetic of rt_hit_surfaces* and
  * rt_light_hits* (DESIGN.md §3.1a), of the shadow term, rt_shadow_hits*
- * and rt_light_hits_shadowed* (§3.1b), and of the mirror bounce,
- * rt_reflect_hits* and rt_light_hits_reflected* (§3.1c): one text for the host
- * functions (csrc/rt_light.cpp) and the kernels (csrc/rt_light.hip,
- * csrc/rt_shadow.hip, csrc/rt_reflect.hip), and their shared argument check.
+ * and rt_light_hits_shadowed* (§3.1b), of the mirror bounce,
+ * rt_reflect_hits* and rt_light_hits_reflected* (§3.1c), and of the two
+ * together, rt_shadow_hits_reflected* and rt_light_hits_shadowed_reflected*
+ * (§3.1d): one text for the host functions (csrc/rt_light.cpp) and the kernels
+ * (csrc/rt_light.hip, csrc/rt_shadow.hip, csrc/rt_reflect.hip,
+ * csrc/rt_shadow_reflect.hip), and their shared argument check.
  * Internal: not installed, not part of the ABI.
  *
  * Every fp32 operation is written on its own and rounds once; both builds
@@ -472,6 +474,87 @@ RT_LIGHT_FN void lit_pixel_reflected(const rt_scene& s, int32_t obj, const float
     if (s.num_lights > 0) k = light_factor(n, p, s.lights, s.num_lights);
     const Vec3 R = mirror_dir(n, d);
     shade_mirrored(s, obj, t, k, p, R, bounce_walk(s, obj, p, R), r, out);
+}
+
+/* ---- shadows and the mirror bounce together --------------
+ * The mirrored pixel with the shadow term in both places: the shadowed factor
+ * at the hit point p and the shadowed factor at the point p2 the bounce meets.
+ *
+ * Who is left out at p2: the bounce's object obj2, always, and nothing else;
+ * the primary pixel's own object is an occluder at p2 like any other.  That is
+ * exact where the bounce arrives from outside obj2 (the argument of the shadow
+ * term above).  It is not exact where it arrives from inside obj2 (the far
+ * root of a sphere p lies in, a triangle of an intersecting cube met from
+ * within): there n2 is turned inward and obj2's far side could hide a facing
+ * light.  The rule is "leave obj2 out" all the same. */
+
+// The point the bounce meets, as shade_mirrored computes it.
+RT_LIGHT_FN Vec3 bounce_point(Vec3 p, Vec3 R, float best) {
+    return Vec3{p.x + best * R.x, p.y + best * R.y, p.z + best * R.z};
+}
+
+// shade_mirrored with both factors given: k at the hit point, k2 at the point
+// the bounce `b` met (read only where it met something).  For a hit pixel
+// with t != kFar.
+RT_LIGHT_FN void shade_mirrored_factors(const rt_scene& s, int32_t obj, float t, float k, Bounce b,
+                                        float k2, float r, int32_t out[4]) {
+    const float normalised = (t - 0.0f) / (180.0f - 0.0f);
+    const float scalar = 255.0f - (normalised * 255.0f);
+    const float lit = scalar * k;
+    const Vec3 colour = slot_colour(s, obj);
+    float lit2 = 0.0f;
+    Vec3 colour2{0.0f, 0.0f, 0.0f};
+    if (b.obj2 >= 0) {
+        const float t2 = t + b.best;
+        const float normalised2 = (t2 - 0.0f) / (180.0f - 0.0f);
+        float scalar2 = 255.0f - (normalised2 * 255.0f);
+        // beyond the ramp's end a mirrored object adds nothing, not negative light
+        if (!(scalar2 > 0.0f)) scalar2 = 0.0f;
+        lit2 = scalar2 * k2;
+        colour2 = slot_colour(s, b.obj2);
+    }
+    const float a[3] = {lit * colour.x, lit * colour.y, lit * colour.z};
+    const float m[3] = {lit2 * colour2.x, lit2 * colour2.y, lit2 * colour2.z};
+    for (int c = 0; c < 3; ++c) out[c] = cvt_i32(a[c] + r * (m[c] - a[c]));
+    out[3] = 255;
+}
+
+// One mirrored, shadowed lit pixel (int32x4), r != 0.  A miss, and t == kFar,
+// are lit_pixel_shadowed's.
+RT_LIGHT_FN void lit_pixel_shadowed_reflected(const rt_scene& s, int32_t obj, const float* verts,
+                                              float ox, float oy, Vec3 d, float t, float r,
+                                              int32_t out[4]) {
+    if (obj < 0 || t == kFar) {
+        lit_pixel_shadowed(s, obj, verts, ox, oy, d, t, out);
+        return;
+    }
+    const Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
+    const Vec3 n{sf.nx, sf.ny, sf.nz};
+    float k = 1.0f;
+    if (s.num_lights > 0) k = shadowed_factor(s, obj, n, p);
+    const Vec3 R = mirror_dir(n, d);
+    const Bounce b = bounce_walk(s, obj, p, R);
+    float k2 = 1.0f;
+    if (b.obj2 >= 0 && s.num_lights > 0) {
+        const Vec3 p2 = bounce_point(p, R, b.best);
+        k2 = shadowed_factor(s, b.obj2, bounce_normal(s, b.obj2, b.tri2, p2, R), p2);
+    }
+    shade_mirrored_factors(s, obj, t, k, b, k2, r, out);
+}
+
+// The mask at the point the bounce meets (0 for a miss, without lights, and
+// where the bounce meets nothing).  t is not looked at, as in bounce_pixel.
+RT_LIGHT_FN uint32_t shadow_reflect_pixel(const rt_scene& s, int32_t obj, const float* verts,
+                                          float ox, float oy, Vec3 d, float t) {
+    if (s.num_lights <= 0 || obj < 0) return 0;
+    const Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
+    const Vec3 R = mirror_dir(Vec3{n.nx, n.ny, n.nz}, d);
+    const Bounce b = bounce_walk(s, obj, p, R);
+    if (b.obj2 < 0) return 0;
+    const Vec3 p2 = bounce_point(p, R, b.best);
+    return shadow_mask(s, b.obj2, bounce_normal(s, b.obj2, b.tri2, p2, R), p2);
 }
 
 }  // namespace rt_light

@@ -27,7 +27,8 @@ __all__ = [
     "deg_to_rad", "encode_png", "EXPORTED_SYMBOLS", "CUBE_OP_DTYPE", "cube_ops", "render_multi",
     "debug_glibc_sincosf", "host_register", "host_unregister", "HIT_DTYPE", "HIT_MISS_T",
     "shade_hits", "SURFACE_DTYPE", "hit_surfaces", "light_hits", "shadow_hits",
-    "reflect_hits", "light_hits_reflected",
+    "reflect_hits", "light_hits_reflected", "shadow_hits_reflected",
+    "light_hits_shadowed_reflected",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -59,7 +60,9 @@ EXPORTED_SYMBOLS = (
     "rt_shade_hits", "rt_hit_surfaces", "rt_light_hits", "rt_hit_surfaces_device",
     "rt_light_hits_device", "rt_shadow_hits", "rt_light_hits_shadowed", "rt_shadow_hits_device",
     "rt_light_hits_shadowed_device", "rt_reflect_hits", "rt_light_hits_reflected",
-    "rt_reflect_hits_device", "rt_light_hits_reflected_device",
+    "rt_reflect_hits_device", "rt_light_hits_reflected_device", "rt_shadow_hits_reflected",
+    "rt_light_hits_shadowed_reflected", "rt_shadow_hits_reflected_device",
+    "rt_light_hits_shadowed_reflected_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -186,6 +189,15 @@ def library() -> ctypes.CDLL:
                                                   i32, vp, vp]),
         "rt_light_hits_reflected_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32,
                                                           i32, i32, f32, i32, vp, vp]),
+        "rt_shadow_hits_reflected": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32,
+                                                    vp]),
+        "rt_light_hits_shadowed_reflected": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32,
+                                                            i32, i32, f32, i32, vp]),
+        "rt_shadow_hits_reflected_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp,
+                                                           i32, i32, i32, vp, vp]),
+        "rt_light_hits_shadowed_reflected_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene),
+                                                                   vp, i32, i32, i32, f32, i32, vp,
+                                                                   vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -542,6 +554,42 @@ def light_hits_reflected(hits: np.ndarray, scene: Scene, reflectivity: float,
     return out
 
 
+def light_hits_shadowed_reflected(hits: np.ndarray, scene: Scene, reflectivity: float,
+                                  fmt: str = "i32x4", rows: Optional[Tuple[int, int]] = None,
+                                  ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_light_hits_shadowed_reflected: light_hits_reflected with the shadow
+    term in both places: a light that another object hides adds nothing at
+    the hit point, nor at the point the pixel mirrors (there every object but
+    the mirrored one can hide it, the pixel's own included).  0 gives
+    light_hits(shadows=True)'s frame bit for bit.  On the host."""
+    if fmt not in ("i32x4", "rgba8"):
+        raise ValueError("light_hits_shadowed_reflected gives an i32x4 or an rgba8 frame")
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
+    sc = scene.as_c()
+    _check(library().rt_light_hits_shadowed_reflected(
+        _ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re, reflectivity, _FORMATS[fmt],
+        _ptr(out)), "rt_light_hits_shadowed_reflected")
+    return out
+
+
+def shadow_hits_reflected(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
+                          ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_shadow_hits_reflected: shadow_hits' mask taken at the point each
+    pixel mirrors: bit i is set iff light i faces that point and an object
+    other than the mirrored one hides it (at most 32 lights); 0 where the
+    pixel mirrors nothing.  On the host."""
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(hits.shape, np.uint32)
+    sc = scene.as_c()
+    _check(library().rt_shadow_hits_reflected(_ptr(hits), ctypes.byref(sc), _ptr(d),
+                                              hits.shape[1], rb, re, _ptr(out)),
+           "rt_shadow_hits_reflected")
+    return out
+
+
 def _device_scene(device_scene: dict) -> _Scene:
     """rt_scene of device addresses, lights included (hit post-passes)."""
     g = device_scene.get
@@ -691,18 +739,35 @@ class RayTracer:
     def light_hits_reflected_device(self, hits_ptr: int, device_scene: dict, width: int,
                                     rows: Tuple[int, int], out_ptr: int, reflectivity: float,
                                     ray_dir: Optional[np.ndarray] = None, stream: int = 0,
-                                    fmt: str = "i32x4") -> None:
+                                    fmt: str = "i32x4", shadows: bool = False) -> None:
         """rt_light_hits_reflected_device: a device hit frame to a lit "i32x4"
         or "rgba8" frame at `out_ptr`, every pixel blended by `reflectivity`
-        with what it mirrors.  Asynchronous on `stream`."""
+        with what it mirrors.  shadows=True:
+        rt_light_hits_shadowed_reflected_device, the shadow term at the hit
+        point and at the mirrored point.  Asynchronous on `stream`."""
         if fmt not in ("i32x4", "rgba8"):
             raise ValueError("light_hits_reflected_device gives an i32x4 or an rgba8 frame")
         d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
         sc = _device_scene(device_scene)
-        _check(library().rt_light_hits_reflected_device(
+        fn, name = ((library().rt_light_hits_shadowed_reflected_device,
+                     "rt_light_hits_shadowed_reflected_device") if shadows
+                    else (library().rt_light_hits_reflected_device,
+                          "rt_light_hits_reflected_device"))
+        _check(fn(self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
+                  reflectivity, _FORMATS[fmt], out_ptr or None, stream or None), name)
+
+    def shadow_hits_reflected_device(self, hits_ptr: int, device_scene: dict, width: int,
+                                     rows: Tuple[int, int], out_ptr: int,
+                                     ray_dir: Optional[np.ndarray] = None,
+                                     stream: int = 0) -> None:
+        """rt_shadow_hits_reflected_device: a device hit frame to one uint32
+        shadow mask per pixel at `out_ptr`, taken at the point the pixel
+        mirrors (at most 32 lights).  Asynchronous on `stream`."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_shadow_hits_reflected_device(
             self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
-            reflectivity, _FORMATS[fmt], out_ptr or None, stream or None),
-            "rt_light_hits_reflected_device")
+            out_ptr or None, stream or None), "rt_shadow_hits_reflected_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,
