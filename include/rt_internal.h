@@ -1,7 +1,8 @@
 /*
  * rt_internal.h -- shared between the library's own translation units
- * (rt_device.hip, rt_scene_device.hip, rt_light.hip, rt_shadow.hip,
- * rt_reflect.hip).  Not installed, not part of the ABI.
+ * (rt_device.hip, rt_scene_device.hip and, through rt_light_device.inc,
+ * rt_light.hip, rt_shadow.hip, rt_reflect.hip, rt_shadow_reflect.hip).  Not
+ * installed, not part of the ABI.
  */
 #ifndef RT_INTERNAL_H
 #define RT_INTERNAL_H

@@ -6,7 +6,8 @@
  * together, rt_shadow_hits_reflected* and rt_light_hits_shadowed_reflected*
  * (§3.1d): one text for the host functions (csrc/rt_light.cpp) and the kernels
  * (csrc/rt_light.hip, csrc/rt_shadow.hip, csrc/rt_reflect.hip,
- * csrc/rt_shadow_reflect.hip), and their shared argument check.
+ * csrc/rt_shadow_reflect.hip; how a wave walks through it is
+ * csrc/rt_light_device.inc), and their shared argument check.
  * Internal: not installed, not part of the ABI.
  *
  * Every fp32 operation is written on its own and rounds once; both builds
@@ -22,7 +23,7 @@
 
 #include "rt_hip.h"
 
-/* rt_light.hip defines this as `__host__ __device__ inline` before including */
+/* rt_light_device.inc defines this as `__host__ __device__ inline` before including */
 #ifndef RT_LIGHT_FN
 #define RT_LIGHT_FN inline
 #endif

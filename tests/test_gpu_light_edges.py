@@ -52,7 +52,7 @@ def test_device_equals_host_and_restatement(pkg, rt, oracle, name):
     hd = upload_hits(torch, hits)
     x0, compared = r.x_begin, []
     for what in OUTPUTS:
-        buf = run_device(pkg, rt, torch, ds, hd, r.w, r.rows, what, r.d)
+        buf = run_device("light", pkg, rt, torch, ds, hd, r.w, r.rows, what, r.d)
         got = unguard(torch, pkg, buf, r.w, r.rows, what)
         del buf
         # the host: the same frame, or, where it refuses the frame's ids, the

@@ -33,7 +33,8 @@ def test_device_equals_host_on_the_base_scene(pkg, rt, w, h, rows):
     assert (hits["object"] >= nc).sum() > 100 and (hits["object"] == -1).sum() > 100
     for lights in ([], ONE_LIGHT, THREE_LIGHTS):
         sl = lr.with_lights(scene, lights)
-        got = compare_all(pkg, rt, torch, sl, hits, w, rows, label=f"{len(lights)} lights")
+        got = compare_all("light", pkg, rt, torch, sl, None, hits, w, rows,
+                          label=f"{len(lights)} lights")
         cube = (hits["object"] >= 0) & (hits["object"] < nc)
         assert (got["surface"]["triangle"][cube] >= 0).all()
         if not lights:  # the trace's own colour frames
@@ -58,7 +59,7 @@ def test_partial_waves_and_workgroups(pkg, rt, w, h):
         scene.sphere_origins[0, :2] = 0
     hits, _ = rt.render(scene, w, h, fmt="hit", ray_dir=REF_DIR)
     assert (hits["object"] >= 0).any()
-    compare_all(pkg, rt, torch, scene, hits, w, (0, h), label=f"{w}x{h}")
+    compare_all("light", pkg, rt, torch, scene, None, hits, w, (0, h), label=f"{w}x{h}")
 
 
 # --- 3. trace, then light, on one stream ------------------------------------------
@@ -77,8 +78,8 @@ def test_trace_then_light_on_one_stream(pkg, rt, oracle):
     with torch.cuda.stream(stream):
         rt.render_device(ds, W, H, (0, H), hd.data_ptr(), ray_dir=np.array(REF_DIR, F32),
                          fmt="hit", stream=stream.cuda_stream)
-        bufs = {fmt: run_device(pkg, rt, torch, ds, hd, W, (0, H), fmt,
-                                stream=stream.cuda_stream) for fmt in ("i32x4", "rgba8")}
+        bufs = {fmt: run_device("light", pkg, rt, torch, ds, hd, W, (0, H), fmt,
+                                 stream=stream.cuda_stream) for fmt in ("i32x4", "rgba8")}
     stream.synchronize()
     assert np.array_equal(hd.cpu().numpy().view(np.uint32), lr.words(hits_ref))
     for fmt, buf in bufs.items():
@@ -104,13 +105,13 @@ def test_numeric_edges_with_lights(pkg, rt, oracle, i):
     ds, keep = device_scene(torch, scene)
     hd = upload_hits(torch, hits)
     for fmt in ("i32x4", "rgba8"):
-        buf = run_device(pkg, rt, torch, ds, hd, w, (0, h), fmt, d)
+        buf = run_device("light", pkg, rt, torch, ds, hd, w, (0, h), fmt, d)
         got = unguard(torch, pkg, buf, w, (0, h), fmt)
         want = pkg.light_hits(hits, scene, fmt, ray_dir=d)
         assert not eq(got, want), f"{key} {fmt}: {eq(got, want)}"
         if key == "minus_inf" and fmt == "i32x4":
             assert (got[np.isneginf(hits["t"])][:, :3] == -(1 << 31)).all()
-    buf = run_device(pkg, rt, torch, ds, hd, w, (0, h), "surface", d)
+    buf = run_device("light", pkg, rt, torch, ds, hd, w, (0, h), "surface", d)
     got = unguard(torch, pkg, buf, w, (0, h), "surface")
     want = pkg.hit_surfaces(hits, scene, ray_dir=d)
     assert np.array_equal(got["triangle"], want["triangle"])
@@ -133,7 +134,7 @@ def test_empty_scene(pkg, rt, lights):
     assert (hits["t"] == K_FAR).all() and (hits["object"] == -1).all()
     ds, _keep = device_scene(torch, scene)
     assert not any(ds.get(k) for k in SCENE_ARRAYS[:5])
-    got = compare_all(pkg, rt, torch, scene, hits, w, (0, h), label="empty")
+    got = compare_all("light", pkg, rt, torch, scene, None, hits, w, (0, h), label="empty")
     assert (got["i32x4"] == (0, 0, 0, 255)).all() and (got["rgba8"] == 0xFF000000).all()
     assert (lr.words(got["surface"]) == np.array([0, 0, 0, 0xFFFFFFFF], np.uint32)).all()
 
@@ -154,7 +155,7 @@ def test_one_cube_fills_the_frame(pkg, rt):
     obj = hits["object"].reshape(-1, 64)  # one row of this view per wave
     assert (hits["object"] >= 0).all()
     assert (obj == 0).all(1).sum() > 200 and ((obj == 0).any(1) & (obj == 1).any(1)).sum() > 10
-    got = compare_all(pkg, rt, torch, scene, hits, w, (0, h), label="one cube")
+    got = compare_all("light", pkg, rt, torch, scene, None, hits, w, (0, h), label="one cube")
     cube = hits["object"] == 0
     front = set(np.nonzero((face.reshape(12, 3, 4)[:, :, 2] == -50).all(1))[0].tolist())
     assert len(front) == 2

@@ -3,7 +3,7 @@
 tests/test_reflect_hits.py pins to the numpy restatement (tests/reflect_ref.py).
 
 Device memory is torch tensors; every output sits between guard words
-(tests/reflect_device.py over tests/light_device.py), and the guard words and
+(tests/light_device.py), and the guard words and
 the hit frame must come back unchanged.  Frames are compared as raw 32-bit
 words; no word is masked (a bounce frame holds no created NaN, a lit channel
 turns every NaN into INT32_MIN: tests/test_reflect_hits.py).
@@ -17,11 +17,12 @@ import reflect_ref as rr
 import shadow_ref as sr
 from gpu_support import H, SCENE_ARRAYS, W, device_scene
 from hit_ref import K_FAR, REF_DIR
-from light_device import PATTERN, check_scene_padding, padded_device_scene, upload_hits
-from light_device import run_device as run_light_device
-from light_device import unguard as unguard_light
+from light_device import (PASSES, PATTERN, check_scene_padding, compare_all, host_result,
+                          padded_device_scene, run_device, unguard, upload_hits)
 from light_ref import ONE_LIGHT, THREE_LIGHTS, base, eq
-from reflect_device import OUTPUTS, compare_all, host_result, run_reflect_device, unguard
+
+P = "reflect"  # this file's pass of tests/light_device.py
+OUTPUTS = PASSES[P].outputs
 
 gpu = pytest.mark.gpu
 F32 = np.float32
@@ -36,7 +37,7 @@ def test_the_four_kinds(pkg, rt, oracle, padded):
     w, h = rr.MIRROR_W, rr.MIRROR_H
     hits = lr.cached_hits(oracle, "mirror", scene, w, h)
     ds, keep = (padded_device_scene if padded else device_scene)(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="kinds")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="kinds")
     obj, o2, nc = hits["object"], got["bounce"]["object"], scene.num_cubes
     for receiver in (obj < nc, obj >= nc):
         for target in ((o2 >= 0) & (o2 < nc), o2 >= nc):
@@ -63,7 +64,7 @@ def test_wave_level_paths(pkg, rt, oracle, lights):
     assert (want["object"] == 1).sum() >= 100  # the unseen sphere, in the whole waves ...
     assert sr.segments(want["object"] >= 0)[2] >= 10
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="waves")
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="waves")
     del keep
 
 
@@ -99,7 +100,7 @@ def test_partial_waves_and_workgroups(pkg, rt, oracle, w, h):
         hits = lr.cached_hits(oracle, "base", scene, w, H if h == 3 else h, rows)
         assert (pkg.reflect_hits(hits, scene, rows=rows)["object"] >= 0).sum() > 5
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, rows, label=f"{w}x{h}")
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, rows, label=f"{w}x{h}")
     del keep
 
 
@@ -119,13 +120,13 @@ def test_trace_then_reflected_light_on_one_stream(pkg, rt, oracle):
     with torch.cuda.stream(stream):
         rt.render_device(ds, W, H, (0, H), hd.data_ptr(), ray_dir=np.array(REF_DIR, F32),
                          fmt="hit", stream=stream.cuda_stream)
-        bufs = {what: run_reflect_device(pkg, rt, torch, ds, hd, W, (0, H), what,
-                                         stream=stream.cuda_stream) for what in OUTPUTS}
+        bufs = {what: run_device(P, pkg, rt, torch, ds, hd, W, (0, H), what,
+                                 stream=stream.cuda_stream) for what in OUTPUTS}
     stream.synchronize()
     assert np.array_equal(hd.cpu().numpy().view(np.uint32), lr.words(hits_ref))
     for what, buf in bufs.items():
         got = unguard(torch, pkg, buf, W, (0, H), what)
-        want = host_result(pkg, hits_ref, scene, (0, H), what)
+        want = host_result(P, pkg, hits_ref, scene, (0, H), what)
         assert not eq(got, want), f"{what}: {eq(got, want)}"
         if what == "bounce":
             assert (got["object"] >= 0).sum() > 300
@@ -141,7 +142,7 @@ def test_256_occluders(pkg, rt):
     assert 12 * scene.num_cubes + scene.num_spheres == 256
     hits, _ = rt.render(scene, W, H, fmt="hit", ray_dir=REF_DIR)
     ds, keep = device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, W, (0, H), label="256 primitives")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, W, (0, H), label="256 primitives")
     o2 = got["bounce"]["object"]
     assert (o2 >= 0).sum() > 50 and len(np.unique(o2)) > 5
     del keep
@@ -166,7 +167,7 @@ def test_foreign_frames(pkg, rt, oracle, kind):
         assert outside.sum() == 36
         for what in OUTPUTS:
             with pytest.raises(pkg.RtError) as e:
-                host_result(pkg, given, scene, (0, H), what)
+                host_result(P, pkg, given, scene, (0, H), what)
             assert e.value.status == pkg.RT_ERR_INVALID_ARG
     else:
         assert not outside.any()
@@ -174,7 +175,7 @@ def test_foreign_frames(pkg, rt, oracle, kind):
         far = (given["t"] == K_FAR) & (obj >= 0)
         assert far.sum() >= 8
     ds, keep = padded_device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, given, W, (0, H), label=f"foreign {kind}",
+    got = compare_all(P, pkg, rt, torch, scene, ds, given, W, (0, H), label=f"foreign {kind}",
                       host_hits=mapped)
     o2 = got["bounce"]["object"]
     assert (o2[outside] == -1).all() and (got["bounce"]["t"][outside] == K_FAR).all()
@@ -191,7 +192,7 @@ def test_numeric_edges(pkg, rt, oracle, name):
     scene, w, h, d, key = rr.edge_cases(pkg)[name]
     hits = lr.cached_hits(oracle, key, scene, w, h, None, d)
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), d=d, label=name)
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), d=d, label=name)
     del keep
 
 
@@ -210,7 +211,7 @@ def test_ties_far_roots_and_the_ramps_end(pkg, rt, oracle, name):
     w, h = 64, 48
     hits = lr.cached_hits(oracle, key, scene, w, h)
     ds, keep = device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label=name)
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label=name)
     if name == "sphere_tie":
         y, x = rr.TIE_PIXEL
         assert got["bounce"]["object"][y, x] == 0
@@ -231,7 +232,7 @@ def test_empty_scene(pkg, rt, lights):
     hits["t"], hits["object"] = K_FAR, -1
     ds, keep = device_scene(torch, scene)
     assert not any(ds.get(k) for k in SCENE_ARRAYS[:5]) and ds["num_lights"] == len(lights)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="empty")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="empty")
     assert (got["bounce"]["object"] == -1).all() and (got["bounce"]["t"] == K_FAR).all()
     assert (got["i32x4"] == (0, 0, 0, 255)).all() and (got["rgba8"] == 0xFF000000).all()
     del keep
@@ -249,10 +250,10 @@ def test_reflectivity_zero_is_light_hits_device(pkg, rt, oracle, lights):
     hd = upload_hits(torch, hits)
     for what in ("i32x4", "rgba8"):
         for refl in (0.0, -0.0):
-            got = unguard(torch, pkg, run_reflect_device(pkg, rt, torch, ds, hd, w, (0, h), what,
-                                                         refl=refl), w, (0, h), what)
-            want = unguard_light(torch, pkg, run_light_device(pkg, rt, torch, ds, hd, w, (0, h),
-                                                              what), w, (0, h), what)
+            got = unguard(torch, pkg, run_device(P, pkg, rt, torch, ds, hd, w, (0, h), what,
+                                                 refl=refl), w, (0, h), what)
+            want = unguard(torch, pkg, run_device("light", pkg, rt, torch, ds, hd, w, (0, h),
+                                                  what), w, (0, h), what)
             assert not eq(got, want), f"{what}: {eq(got, want)}"
             assert not eq(got, pkg.light_hits(hits, scene, what)), what
     del keep

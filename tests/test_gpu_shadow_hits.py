@@ -3,7 +3,7 @@
 tests/test_shadow_hits.py pins to the numpy restatement (tests/shadow_ref.py).
 
 Device memory is torch tensors; every output sits between guard words
-(tests/shadow_device.py over tests/light_device.py), and the guard words and
+(tests/light_device.py), and the guard words and
 the hit frame must come back unchanged.  Frames are compared as raw 32-bit
 words.
 """
@@ -15,9 +15,12 @@ import light_ref as lr
 import shadow_ref as sr
 from gpu_support import H, SCENE_ARRAYS, W, device_scene
 from hit_ref import K_FAR, REF_DIR
-from light_device import PATTERN, check_scene_padding, padded_device_scene
+from light_device import (PASSES, PATTERN, check_scene_padding, compare_all, host_result,
+                          padded_device_scene, run_device, unguard)
 from light_ref import ONE_LIGHT, THREE_LIGHTS, base, eq
-from shadow_device import OUTPUTS, compare_all, host_result, run_shadow_device, unguard
+
+P = "shadow"  # this file's pass of tests/light_device.py
+OUTPUTS = PASSES[P].outputs
 
 gpu = pytest.mark.gpu
 F32 = np.float32
@@ -32,7 +35,7 @@ def test_the_four_kinds(pkg, rt, oracle, padded):
     w, h = sr.KINDS_W, sr.KINDS_H
     hits = lr.cached_hits(oracle, "shadow_kinds", scene, w, h)
     ds, keep = (padded_device_scene if padded else device_scene)(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="kinds")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="kinds")
     assert (got["mask"] == 1).sum() > 1000 and set(np.unique(got["mask"]).tolist()) == {0, 1}
     if padded:
         check_scene_padding(torch, scene, keep)
@@ -54,7 +57,7 @@ def test_wave_level_paths(pkg, rt, oracle):
     full, none, mixed = sr.segments(r.mask != 0)  # the restatement: 61, 106, 89
     assert full >= 30 and none >= 30 and mixed >= 10
     ds, keep = device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="waves")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="waves")
     assert np.array_equal(got["mask"], r.mask) and not eq(got["i32x4"], r.lit)
     del keep
 
@@ -86,7 +89,7 @@ def test_partial_waves_and_workgroups(pkg, rt, oracle, w, h):
         hits = lr.cached_hits(oracle, "base", scene, w, h)
         assert (pkg.shadow_hits(hits, scene) != 0).sum() > 5
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label=f"{w}x{h}")
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label=f"{w}x{h}")
     del keep
 
 
@@ -106,13 +109,13 @@ def test_trace_then_shadowed_light_on_one_stream(pkg, rt, oracle):
     with torch.cuda.stream(stream):
         rt.render_device(ds, W, H, (0, H), hd.data_ptr(), ray_dir=np.array(REF_DIR, F32),
                          fmt="hit", stream=stream.cuda_stream)
-        bufs = {what: run_shadow_device(pkg, rt, torch, ds, hd, W, (0, H), what,
-                                        stream=stream.cuda_stream) for what in OUTPUTS}
+        bufs = {what: run_device(P, pkg, rt, torch, ds, hd, W, (0, H), what,
+                                 stream=stream.cuda_stream) for what in OUTPUTS}
     stream.synchronize()
     assert np.array_equal(hd.cpu().numpy().view(np.uint32), lr.words(hits_ref))
     for what, buf in bufs.items():
-        got = unguard(torch, buf, W, (0, H), what)
-        want = host_result(pkg, hits_ref, scene, (0, H), what)
+        got = unguard(torch, pkg, buf, W, (0, H), what)
+        want = host_result(P, pkg, hits_ref, scene, (0, H), what)
         assert not eq(got, want), f"{what}: {eq(got, want)}"
         if what == "mask":
             assert (got != 0).sum() > 20
@@ -128,7 +131,7 @@ def test_256_occluders(pkg, rt):
     assert 12 * scene.num_cubes + scene.num_spheres == 256
     hits, _ = rt.render(scene, W, H, fmt="hit", ray_dir=REF_DIR)
     ds, keep = device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, W, (0, H), label="256 occluders")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, W, (0, H), label="256 occluders")
     assert (got["mask"] != 0).sum() > 50 and len(np.unique(got["mask"])) > 2
     del keep
 
@@ -152,12 +155,12 @@ def test_foreign_frames(pkg, rt, oracle, kind):
         assert outside.sum() == 36
         for what in OUTPUTS:
             with pytest.raises(pkg.RtError) as e:
-                host_result(pkg, given, scene, (0, H), what)
+                host_result(P, pkg, given, scene, (0, H), what)
             assert e.value.status == pkg.RT_ERR_INVALID_ARG
     else:
         assert not outside.any()
     ds, keep = padded_device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, given, W, (0, H), label=f"foreign {kind}",
+    got = compare_all(P, pkg, rt, torch, scene, ds, given, W, (0, H), label=f"foreign {kind}",
                       host_hits=mapped)
     assert (got["mask"][outside] == 0).all() and (got["mask"] != 0).sum() > 20
     check_scene_padding(torch, scene, keep)
@@ -176,7 +179,7 @@ def test_numeric_edges(pkg, rt, oracle, name):
     key = "shadow_kinds" if name in sr.EDGE_LIGHTS else "shadow_edge_" + name
     hits = lr.cached_hits(oracle, key, scene, w, h, None, d)
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), d=d, label=name)
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), d=d, label=name)
     del keep
 
 
@@ -192,7 +195,7 @@ def test_empty_scene(pkg, rt, lights):
     hits["t"], hits["object"] = K_FAR, -1
     ds, keep = device_scene(torch, scene)
     assert not any(ds.get(k) for k in SCENE_ARRAYS[:5]) and ds["num_lights"] == len(lights)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="empty")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="empty")
     assert not got["mask"].any()
     assert (got["i32x4"] == (0, 0, 0, 255)).all() and (got["rgba8"] == 0xFF000000).all()
     del keep

@@ -4,7 +4,7 @@ the GPU: the kernel (csrc/rt_shadow_reflect.hip) against the host functions
 restatement (tests/shadow_reflect_ref.py).
 
 Device memory is torch tensors; every output sits between guard words
-(tests/shadow_reflect_device.py over tests/light_device.py), and the guard
+(tests/light_device.py), and the guard
 words and the hit frame must come back unchanged.  Frames are compared as raw
 32-bit words; no word is masked (a mask holds no NaN, a lit channel turns
 every NaN into INT32_MIN).
@@ -19,16 +19,14 @@ import shadow_ref as sr
 import shadow_reflect_ref as srr
 from gpu_support import H, SCENE_ARRAYS, W, device_scene
 from hit_ref import K_FAR, REF_DIR
-from light_device import PATTERN, check_scene_padding, padded_device_scene, upload_hits
+from light_device import (PASSES, PATTERN, check_scene_padding, compare_all, host_result,
+                          padded_device_scene, run_device, unguard, upload_hits)
 from light_ref import ONE_LIGHT, THREE_LIGHTS, base, eq
-from reflect_device import run_reflect_device
-from reflect_device import unguard as unguard_reflect
-from shadow_device import run_shadow_device
-from shadow_device import unguard as unguard_shadow
-from shadow_reflect_device import (OUTPUTS, compare_all, host_result, run_shadow_reflect_device,
-                                   unguard)
 from test_gpu_reflect_hits import lone_pixel_scene
 from test_shadow_reflect_hits import INSIDE_LIGHTS, SPECIAL_NAMES, class_facts, special_scenes
+
+P = "shadow_reflect"  # this file's pass of tests/light_device.py
+OUTPUTS = PASSES[P].outputs
 
 gpu = pytest.mark.gpu
 F32 = np.float32
@@ -44,7 +42,7 @@ def test_the_classes(pkg, rt, oracle, padded):
     hits = lr.cached_hits(oracle, "shadow_reflect_class", scene, w, h)
     class_facts(scene, hits, srr.shadow_reflect_ref(oracle, scene, hits))
     ds, keep = (padded_device_scene if padded else device_scene)(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="classes")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="classes")
     assert (got["mask2"] == 1).sum() >= 100 and (got["mask2"] == 2).sum() >= 100
     if padded:
         check_scene_padding(torch, scene, keep)
@@ -79,7 +77,7 @@ def test_wave_level_paths(pkg, rt, oracle, lights):
         assert (hit2.any(1) & faces2.any(1)).sum() >= 50  # 103
         assert sr.segments(c.at_p2.cast.any(0))[2] >= 50  # a partial pending set
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="waves")
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="waves")
     del keep
 
 
@@ -103,7 +101,7 @@ def test_partial_waves_and_workgroups(pkg, rt, oracle, w, h):
         hits = lr.cached_hits(oracle, "base", scene, w, H if h == 3 else h, rows)
         assert (pkg.reflect_hits(hits, scene, rows=rows)["object"] >= 0).sum() > 5
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, rows, label=f"{w}x{h}")
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, rows, label=f"{w}x{h}")
     del keep
 
 
@@ -123,20 +121,20 @@ def test_trace_then_reflect_then_shadowed_reflected_light_on_one_stream(pkg, rt,
     with torch.cuda.stream(stream):
         rt.render_device(ds, W, H, (0, H), hd.data_ptr(), ray_dir=np.array(REF_DIR, F32),
                          fmt="hit", stream=stream.cuda_stream)
-        first = {what: run_shadow_reflect_device(pkg, rt, torch, ds, hd, W, (0, H), what,
-                                                 stream=stream.cuda_stream) for what in OUTPUTS}
-        bounce = run_reflect_device(pkg, rt, torch, ds, hd, W, (0, H), "bounce",
-                                    stream=stream.cuda_stream)
-        second = {what: run_shadow_reflect_device(pkg, rt, torch, ds, hd, W, (0, H), what,
-                                                  stream=stream.cuda_stream) for what in OUTPUTS}
+        first = {what: run_device(P, pkg, rt, torch, ds, hd, W, (0, H), what,
+                                  stream=stream.cuda_stream) for what in OUTPUTS}
+        bounce = run_device("reflect", pkg, rt, torch, ds, hd, W, (0, H), "bounce",
+                            stream=stream.cuda_stream)
+        second = {what: run_device(P, pkg, rt, torch, ds, hd, W, (0, H), what,
+                                   stream=stream.cuda_stream) for what in OUTPUTS}
     stream.synchronize()
     assert np.array_equal(hd.cpu().numpy().view(np.uint32), lr.words(hits_ref))
-    got = unguard_reflect(torch, pkg, bounce, W, (0, H), "bounce")
+    got = unguard(torch, pkg, bounce, W, (0, H), "bounce")
     assert not eq(got, pkg.reflect_hits(hits_ref, scene)) and (got["object"] >= 0).sum() > 300
     for bufs in (first, second):
         for what, buf in bufs.items():
-            got = unguard(torch, buf, W, (0, H), what)
-            want = host_result(pkg, hits_ref, scene, (0, H), what)
+            got = unguard(torch, pkg, buf, W, (0, H), what)
+            want = host_result(P, pkg, hits_ref, scene, (0, H), what)
             assert not eq(got, want), f"{what}: {eq(got, want)}"
             if what == "mask2":
                 assert (got != 0).sum() >= 20
@@ -152,7 +150,7 @@ def test_256_occluders(pkg, rt):
     assert 12 * scene.num_cubes + scene.num_spheres == 256
     hits, _ = rt.render(scene, W, H, fmt="hit", ray_dir=REF_DIR)
     ds, keep = device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, W, (0, H), label="256 primitives")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, W, (0, H), label="256 primitives")
     assert (got["mask2"] != 0).sum() > 20 and len(np.unique(got["mask2"])) >= 3
     del keep
 
@@ -177,7 +175,7 @@ def test_foreign_frames(pkg, rt, oracle, kind):
         assert outside.sum() == 36 and set(np.unique(obj[outside])) == {-2, n_slots, n_slots + 1}
         for what in OUTPUTS:
             with pytest.raises(pkg.RtError) as e:
-                host_result(pkg, given, scene, (0, H), what)
+                host_result(P, pkg, given, scene, (0, H), what)
             assert e.value.status == pkg.RT_ERR_INVALID_ARG
     else:
         assert not outside.any()
@@ -185,7 +183,7 @@ def test_foreign_frames(pkg, rt, oracle, kind):
         far = (given["t"] == K_FAR) & (obj >= 0)
         assert far.sum() >= 8
     ds, keep = padded_device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, given, W, (0, H), label=f"foreign {kind}",
+    got = compare_all(P, pkg, rt, torch, scene, ds, given, W, (0, H), label=f"foreign {kind}",
                       host_hits=mapped)
     assert not got["mask2"][outside].any() and (got["mask2"] != 0).sum() >= 20
     check_scene_padding(torch, scene, keep)
@@ -200,7 +198,7 @@ def test_numeric_edges(pkg, rt, oracle, name):
     scene, w, h, d, key = rr.edge_cases(pkg)[name]
     hits = lr.cached_hits(oracle, key, scene, w, h, None, d)
     ds, keep = device_scene(torch, scene)
-    compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), d=d, label=name)
+    compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), d=d, label=name)
     del keep
 
 
@@ -216,7 +214,7 @@ def test_ties_far_roots_and_the_ramps_end(pkg, rt, oracle, name):
     w, h = 64, 48
     hits = lr.cached_hits(oracle, key, scene, w, h)
     ds, keep = device_scene(torch, scene)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label=name)
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label=name)
     if name == "inside_a_sphere":
         assert (got["mask2"] & 2).any() and ((got["mask2"] & 2) == 0).sum() > 100
     del keep
@@ -234,7 +232,7 @@ def test_empty_scene(pkg, rt, lights):
     hits["t"], hits["object"] = K_FAR, -1
     ds, keep = device_scene(torch, scene)
     assert not any(ds.get(k) for k in SCENE_ARRAYS[:5]) and ds["num_lights"] == len(lights)
-    got = compare_all(pkg, rt, torch, scene, ds, hits, w, (0, h), label="empty")
+    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="empty")
     assert not got["mask2"].any()
     assert (got["i32x4"] == (0, 0, 0, 255)).all() and (got["rgba8"] == 0xFF000000).all()
     del keep
@@ -251,12 +249,12 @@ def test_reflectivity_zero_is_the_shadow_kernels_frame(pkg, rt, oracle, lights):
     ds, keep = device_scene(torch, scene)
     hd = upload_hits(torch, hits)
     for what in ("i32x4", "rgba8"):
-        want = unguard_shadow(torch, run_shadow_device(pkg, rt, torch, ds, hd, w, (0, h), what),
-                              w, (0, h), what)
+        want = unguard(torch, pkg, run_device("shadow", pkg, rt, torch, ds, hd, w, (0, h), what),
+                       w, (0, h), what)
         assert not eq(want, pkg.light_hits(hits, scene, what, shadows=True)), what
         for refl in (0.0, -0.0):
-            got = unguard(torch, run_shadow_reflect_device(pkg, rt, torch, ds, hd, w, (0, h), what,
-                                                           refl=refl), w, (0, h), what)
+            got = unguard(torch, pkg, run_device(P, pkg, rt, torch, ds, hd, w, (0, h), what,
+                                                 refl=refl), w, (0, h), what)
             assert not eq(got, want), f"{what}: {eq(got, want)}"
     del keep
 
@@ -272,14 +270,14 @@ def test_without_lights_it_is_the_reflect_kernels_frame(pkg, rt, oracle):
     hd = upload_hits(torch, hits)
     for what in ("i32x4", "rgba8"):
         for refl in (0.25, 1.0):
-            want = unguard_reflect(torch, pkg, run_reflect_device(pkg, rt, torch, ds, hd, w,
-                                                                  (0, h), what, refl=refl),
-                                   w, (0, h), what)
+            want = unguard(torch, pkg, run_device("reflect", pkg, rt, torch, ds, hd, w,
+                                                  (0, h), what, refl=refl),
+                           w, (0, h), what)
             assert not eq(want, pkg.light_hits_reflected(hits, scene, refl, what)), what
-            got = unguard(torch, run_shadow_reflect_device(pkg, rt, torch, ds, hd, w, (0, h), what,
-                                                           refl=refl), w, (0, h), what)
+            got = unguard(torch, pkg, run_device(P, pkg, rt, torch, ds, hd, w, (0, h), what,
+                                                 refl=refl), w, (0, h), what)
             assert not eq(got, want), f"{what} r={refl}: {eq(got, want)}"
-    got = unguard(torch, run_shadow_reflect_device(pkg, rt, torch, ds, hd, w, (0, h), "mask2"),
+    got = unguard(torch, pkg, run_device(P, pkg, rt, torch, ds, hd, w, (0, h), "mask2"),
                   w, (0, h), "mask2")
     assert not got.any()
     del keep
