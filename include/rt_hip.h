@@ -513,6 +513,69 @@ int rt_light_hits_shadowed_reflected_device(rt_ctx* ctx, const rt_hit* device_hi
                                             float reflectivity, int32_t out_format,
                                             void* device_out, void* stream);
 
+/* ---- mirror chains, reflectivity per object ----------- */
+/* The bounce of rt_reflect_hits* taken again from the point it meets, up to
+ * RT_MAX_BOUNCES times, with one reflectivity per colour slot.
+ *
+ * Level 0 of a pixel's chain is the pixel itself (object, hit point p_0, faced
+ * normal n_0, direction D_0 = ray_dir, depth T_0 = t).  From level j the chain
+ * goes on iff j < max_bounces and reflectivity[obj_j] != 0: along
+ * R_j = mirror(n_j, D_j), over every object but obj_j alone (the primary
+ * object and every earlier one are candidates again), to the closest hit; its
+ * object, point, faced normal, R_j and T_j + the bounce's parameter are level
+ * j + 1.  A level's own colour is a_j = (ramp(T_j) * k_j) * colour_j, the ramp
+ * clamped at 0 from below for j >= 1, k_j the direct light at p_j (shadowed
+ * with `shadows`: occluders are every object but obj_j; 1 without lights).
+ * Where the chain ends at a level its colour is that level's own; where it
+ * ends in a miss, black.  Backwards from there,
+ * C_j = a_j + reflectivity[obj_j] * (C_{j+1} - a_j), and the pixel is
+ * (int)C_0, alpha 255.
+ *
+ * rt_light_hits_mirrored*: that frame.  reflectivity: num_cubes + num_spheres
+ * floats by colour slot (cubes, then spheres).  max_bounces == 1 with one
+ * value r everywhere is rt_light_hits_reflected's frame word for word (with
+ * `shadows`, rt_light_hits_shadowed_reflected's); max_bounces == 0, or an
+ * all-zero array, is rt_light_hits' (rt_light_hits_shadowed's), without a
+ * walk.  Misses and pixels with t == 300000 are those functions' pixels for
+ * every array and depth.
+ * rt_bounce_hits*: one rt_hit per pixel, the geometry of bounce number
+ * `bounce` (1-based) of that chain, followed without regard to reflectivity,
+ * lights or t: the parameter along R_{bounce-1} and the colour slot met.
+ * (300000, -1) for a primary miss, where this bounce or an earlier one meets
+ * nothing, and where a normal is NaN.  bounce == 1 is rt_reflect_hits' frame.
+ *
+ * Leaving only the current object out is exact where a bounce arrives from
+ * outside the object it meets, and has the inexactness stated above for
+ * rt_shadow_hits_reflected where it arrives from inside: the next bounce and
+ * the shadow walk there leave that object out all the same.
+ *
+ * RT_ERR_INVALID_ARG for max_bounces outside [0, RT_MAX_BOUNCES], bounce
+ * outside [1, RT_MAX_BOUNCES], shadows other than 0 or 1, a NULL reflectivity
+ * while max_bounces > 0 and the scene has objects, and (host) any
+ * reflectivity[i] outside [0, 1] or NaN.  The device calls check what the host
+ * can see, the 4-byte alignment of device_reflectivity included; the kernel
+ * reads a value outside [0, 1], NaN included, as 0.  Arguments, alignment (the
+ * bounce frame: 8 bytes), the 2^39-pixel launch limit, the handling of
+ * `object` and asynchrony are those of rt_light_hits / rt_light_hits_device;
+ * one launch, no workspace.  Host and device results are bit-identical. */
+#define RT_MAX_BOUNCES 8
+int rt_bounce_hits(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                   int32_t width, int32_t row_begin, int32_t row_end, int32_t bounce,
+                   rt_hit* out);
+int rt_bounce_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
+                          const float ray_dir[4], int32_t width, int32_t row_begin,
+                          int32_t row_end, int32_t bounce, rt_hit* device_out, void* stream);
+int rt_light_hits_mirrored(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                           int32_t width, int32_t row_begin, int32_t row_end,
+                           const float* reflectivity, int32_t max_bounces, int32_t shadows,
+                           int32_t out_format, void* out);
+int rt_light_hits_mirrored_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                  const rt_scene* device_scene, const float ray_dir[4],
+                                  int32_t width, int32_t row_begin, int32_t row_end,
+                                  const float* device_reflectivity, int32_t max_bounces,
+                                  int32_t shadows, int32_t out_format, void* device_out,
+                                  void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

@@ -4,9 +4,10 @@
  * and rt_light_hits_shadowed* (§3.1b), of the mirror bounce,
  * rt_reflect_hits* and rt_light_hits_reflected* (§3.1c), and of the two
  * together, rt_shadow_hits_reflected* and rt_light_hits_shadowed_reflected*
- * (§3.1d): one text for the host functions (csrc/rt_light.cpp) and the kernels
+ * (§3.1d), and of the mirror chain, rt_bounce_hits* and rt_light_hits_mirrored*
+ * (§3.1e): one text for the host functions (csrc/rt_light.cpp) and the kernels
  * (csrc/rt_light.hip, csrc/rt_shadow.hip, csrc/rt_reflect.hip,
- * csrc/rt_shadow_reflect.hip; how a wave walks through it is
+ * csrc/rt_shadow_reflect.hip, csrc/rt_mirror.hip; how a wave walks through it is
  * csrc/rt_light_device.inc), and their shared argument check.
  * Internal: not installed, not part of the ABI.
  *
@@ -556,6 +557,125 @@ RT_LIGHT_FN uint32_t shadow_reflect_pixel(const rt_scene& s, int32_t obj, const 
     if (b.obj2 < 0) return 0;
     const Vec3 p2 = bounce_point(p, R, b.best);
     return shadow_mask(s, b.obj2, bounce_normal(s, b.obj2, b.tri2, p2, R), p2);
+}
+
+/* ---- mirror chains, reflectivity per object --------------
+ * The bounce taken again from the point it meets, level by level.  Level 0 is
+ * the pixel; from level j the chain goes on iff j < max_bounces and
+ * reflectivity[obj_j] != 0, along R_j = mirror_dir(n_j, D_j), by bounce_walk
+ * with obj_j alone left out: the primary object and every earlier one are
+ * candidates again.  What it meets is level j + 1: obj2, bounce_point,
+ * bounce_normal, D = R_j, T = T_j + best.
+ *
+ * Leaving only the current object out is exact where the bounce arrived from
+ * outside it, and has §3.1d's inexactness where it arrived from inside (the
+ * far root of a sphere, a triangle of an intersecting cube met from within):
+ * the next bounce and the shadow walk there leave that object out all the
+ * same. */
+
+// reflectivity[obj] as the chain reads it: a value not in [0, 1], NaN
+// included, is 0 (the host functions refuse such an array; a kernel cannot).
+// -0 stays -0 and ends the chain like 0.
+RT_LIGHT_FN float slot_reflectivity(const float* reflectivity, int32_t obj) {
+    const float r = reflectivity[obj];
+    return (r >= 0.0f && r <= 1.0f) ? r : 0.0f;
+}
+
+// The ramp of a level at depth T, as shade_mirrored_factors writes it; from
+// level 1 on clamped at 0 from below (NaN: 0).
+RT_LIGHT_FN float chain_scalar(float T, bool clamped) {
+    const float normalised = (T - 0.0f) / (180.0f - 0.0f);
+    float scalar = 255.0f - (normalised * 255.0f);
+    if (clamped && !(scalar > 0.0f)) scalar = 0.0f;
+    return scalar;
+}
+
+// The own colour of a level: (scalar * k) * colour.
+RT_LIGHT_FN Vec3 chain_colour(float scalar, float k, Vec3 colour) {
+    const float lit = scalar * k;
+    return Vec3{lit * colour.x, lit * colour.y, lit * colour.z};
+}
+
+// One step of the backward blend: a + r * (C - a) per channel.
+RT_LIGHT_FN Vec3 chain_blend(Vec3 a, float r, Vec3 C) {
+    return Vec3{a.x + r * (C.x - a.x), a.y + r * (C.y - a.y), a.z + r * (C.z - a.z)};
+}
+
+// The geometry of bounce number `bounce` (1 .. RT_MAX_BOUNCES) of one pixel's
+// chain, followed without regard to reflectivity, lights or t.  (kFar, -1) for
+// a miss and where this bounce or an earlier one met nothing.
+RT_LIGHT_FN Bounce bounce_chain_pixel(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                                      float oy, Vec3 d, float t, int32_t bounce) {
+    if (obj < 0) return Bounce{kFar, -1, -1};
+    Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
+    Vec3 n{sf.nx, sf.ny, sf.nz};
+    Vec3 D = d;
+    for (int32_t j = 1;; ++j) {
+        const Vec3 R = mirror_dir(n, D);
+        const Bounce b = bounce_walk(s, obj, p, R);
+        if (b.obj2 < 0 || j >= bounce) return b;
+        const Vec3 p2 = bounce_point(p, R, b.best);
+        n = bounce_normal(s, b.obj2, b.tri2, p2, R);
+        p = p2;
+        obj = b.obj2;
+        D = R;
+    }
+}
+
+// One pixel of the mirrored frame (int32x4): a chain of at most `max_bounces`
+// (0 .. RT_MAX_BOUNCES) bounces, blended backwards.  `reflectivity` is read at
+// the slots of levels below max_bounces only.  A miss, and t == kFar, are
+// lit_pixel's (with `shadows`, lit_pixel_shadowed's).
+RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                                    float oy, Vec3 d, float t, const float* reflectivity,
+                                    int32_t max_bounces, bool shadows, int32_t out[4]) {
+    if (obj < 0 || t == kFar) {
+        if (shadows)
+            lit_pixel_shadowed(s, obj, verts, ox, oy, d, t, out);
+        else
+            lit_pixel(s, obj, verts, ox, oy, d, t, out);
+        return;
+    }
+    Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
+    Vec3 n{sf.nx, sf.ny, sf.nz};
+    Vec3 D = d;
+    float T = t;
+    Vec3 a[RT_MAX_BOUNCES];  // the levels the chain went on from
+    float r[RT_MAX_BOUNCES];
+    Vec3 C{0.0f, 0.0f, 0.0f};
+    int32_t j = 0;
+    for (;; ++j) {
+        float k = 1.0f;
+        if (s.num_lights > 0)
+            k = shadows ? shadowed_factor(s, obj, n, p) : light_factor(n, p, s.lights, s.num_lights);
+        const Vec3 own = chain_colour(chain_scalar(T, j >= 1), k, slot_colour(s, obj));
+        const float rj = j < max_bounces ? slot_reflectivity(reflectivity, obj) : 0.0f;
+        if (!(rj != 0.0f)) {  // by depth or by a matte object: C_J = a_J
+            C = own;
+            break;
+        }
+        a[j] = own;
+        r[j] = rj;
+        const Vec3 R = mirror_dir(n, D);
+        const Bounce b = bounce_walk(s, obj, p, R);
+        if (b.obj2 < 0) {  // by a miss after level j: C_{j+1} = (0, 0, 0)
+            ++j;
+            break;
+        }
+        const Vec3 p2 = bounce_point(p, R, b.best);
+        n = bounce_normal(s, b.obj2, b.tri2, p2, R);
+        p = p2;
+        obj = b.obj2;
+        D = R;
+        T = T + b.best;
+    }
+    for (int32_t l = j - 1; l >= 0; --l) C = chain_blend(a[l], r[l], C);
+    out[0] = cvt_i32(C.x);
+    out[1] = cvt_i32(C.y);
+    out[2] = cvt_i32(C.z);
+    out[3] = 255;
 }
 
 }  // namespace rt_light

@@ -28,7 +28,7 @@ __all__ = [
     "debug_glibc_sincosf", "host_register", "host_unregister", "HIT_DTYPE", "HIT_MISS_T",
     "shade_hits", "SURFACE_DTYPE", "hit_surfaces", "light_hits", "shadow_hits",
     "reflect_hits", "light_hits_reflected", "shadow_hits_reflected",
-    "light_hits_shadowed_reflected",
+    "light_hits_shadowed_reflected", "RT_MAX_BOUNCES", "bounce_hits", "light_hits_mirrored",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -38,6 +38,7 @@ RT_ERR_OUT_OF_MEMORY, RT_ERR_UNSUPPORTED = -4, -5
 RT_FORMAT_I32X4, RT_FORMAT_RGBA8 = 0, 1
 RT_FORMAT_HIT = 3  # (2 is reserved: RT_ERR_INVALID_ARG)
 RT_PATH_AUTO, RT_PATH_BINNED, RT_PATH_GENERIC = 0, 1, 2
+RT_MAX_BOUNCES = 8  # the longest mirror chain of light_hits_mirrored / bounce_hits
 _FORMATS = {"i32x4": RT_FORMAT_I32X4, "rgba8": RT_FORMAT_RGBA8, "hit": RT_FORMAT_HIT}
 # rt_hit (include/rt_hip.h): one pixel of a "hit" frame.  A miss is
 # (HIT_MISS_T, -1); object is the colour slot (cube c: c, sphere i: num_cubes + i).
@@ -62,7 +63,8 @@ EXPORTED_SYMBOLS = (
     "rt_light_hits_shadowed_device", "rt_reflect_hits", "rt_light_hits_reflected",
     "rt_reflect_hits_device", "rt_light_hits_reflected_device", "rt_shadow_hits_reflected",
     "rt_light_hits_shadowed_reflected", "rt_shadow_hits_reflected_device",
-    "rt_light_hits_shadowed_reflected_device",
+    "rt_light_hits_shadowed_reflected_device", "rt_bounce_hits", "rt_bounce_hits_device",
+    "rt_light_hits_mirrored", "rt_light_hits_mirrored_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -198,6 +200,13 @@ def library() -> ctypes.CDLL:
         "rt_light_hits_shadowed_reflected_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene),
                                                                    vp, i32, i32, i32, f32, i32, vp,
                                                                    vp]),
+        "rt_bounce_hits": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32, i32, vp]),
+        "rt_bounce_hits_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32, i32,
+                                                 i32, i32, vp, vp]),
+        "rt_light_hits_mirrored": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, i32, i32, i32,
+                                                  vp, i32, i32, i32, vp]),
+        "rt_light_hits_mirrored_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32,
+                                                         i32, i32, vp, i32, i32, i32, vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -590,6 +599,54 @@ def shadow_hits_reflected(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[i
     return out
 
 
+def bounce_hits(hits: np.ndarray, scene: Scene, bounce: int,
+                rows: Optional[Tuple[int, int]] = None,
+                ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_bounce_hits: reflect_hits taken again from the point it meets:
+    bounce number `bounce` (1 .. RT_MAX_BOUNCES) of every pixel's mirror chain,
+    each bounce leaving out only the object it starts on, as a HIT_DTYPE array
+    (the parameter along that bounce's direction, the colour slot met);
+    (HIT_MISS_T, -1) where this bounce or an earlier one meets nothing.
+    bounce=1 is reflect_hits' frame.  On the host."""
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(hits.shape, HIT_DTYPE)
+    sc = scene.as_c()
+    _check(library().rt_bounce_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
+                                    int(bounce), _ptr(out)), "rt_bounce_hits")
+    return out
+
+
+def light_hits_mirrored(hits: np.ndarray, scene: Scene, reflectivity, max_bounces: int,
+                        fmt: str = "i32x4", shadows: bool = False,
+                        rows: Optional[Tuple[int, int]] = None,
+                        ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_light_hits_mirrored: light_hits with a mirror chain of at most
+    `max_bounces` (0 .. RT_MAX_BOUNCES) bounces per pixel and one
+    `reflectivity` in [0, 1] per colour slot (cubes, then spheres; None where
+    max_bounces is 0 or the scene is empty): a chain goes on from an object
+    whose reflectivity is not 0, and the levels are blended backwards, each by
+    its object's reflectivity.  shadows=True: the shadow term at every level.
+    max_bounces=1 with one value everywhere is light_hits_reflected's
+    (light_hits_shadowed_reflected's) frame bit for bit.  On the host."""
+    if fmt not in ("i32x4", "rgba8"):
+        raise ValueError("light_hits_mirrored gives an i32x4 or an rgba8 frame")
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    refl = None
+    if reflectivity is not None:
+        refl = np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
+        if refl.size != scene.num_cubes + scene.num_spheres:
+            raise ValueError(f"reflectivity must hold one value per colour slot "
+                             f"({scene.num_cubes + scene.num_spheres}), got {refl.size}")
+    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
+    sc = scene.as_c()
+    _check(library().rt_light_hits_mirrored(
+        _ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re, _ptr(refl),
+        int(max_bounces), int(shadows), _FORMATS[fmt], _ptr(out)), "rt_light_hits_mirrored")
+    return out
+
+
 def _device_scene(device_scene: dict) -> _Scene:
     """rt_scene of device addresses, lights included (hit post-passes)."""
     g = device_scene.get
@@ -768,6 +825,39 @@ class RayTracer:
         _check(library().rt_shadow_hits_reflected_device(
             self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
             out_ptr or None, stream or None), "rt_shadow_hits_reflected_device")
+
+    def bounce_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
+                           rows: Tuple[int, int], out_ptr: int, bounce: int,
+                           ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
+        """rt_bounce_hits_device: a device hit frame to the hit frame of bounce
+        number `bounce` (1 .. RT_MAX_BOUNCES) of its mirror chains at `out_ptr`
+        (8-byte aligned).  Asynchronous on `stream`."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_bounce_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
+                                               _ptr(d), width, rows[0], rows[1], int(bounce),
+                                               out_ptr or None, stream or None),
+               "rt_bounce_hits_device")
+
+    def light_hits_mirrored_device(self, hits_ptr: int, device_scene: dict, width: int,
+                                   rows: Tuple[int, int], out_ptr: int, reflectivity_ptr: int,
+                                   max_bounces: int, ray_dir: Optional[np.ndarray] = None,
+                                   stream: int = 0, fmt: str = "i32x4",
+                                   shadows: bool = False) -> None:
+        """rt_light_hits_mirrored_device: a device hit frame to a lit "i32x4"
+        or "rgba8" frame at `out_ptr` with mirror chains of at most
+        `max_bounces` bounces; `reflectivity_ptr`: the device address of one
+        float per colour slot (a value outside [0, 1] reads as 0).
+        shadows=True: the shadow term at every level.  One launch,
+        asynchronous on `stream`."""
+        if fmt not in ("i32x4", "rgba8"):
+            raise ValueError("light_hits_mirrored_device gives an i32x4 or an rgba8 frame")
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_light_hits_mirrored_device(
+            self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
+            reflectivity_ptr or None, int(max_bounces), int(shadows), _FORMATS[fmt],
+            out_ptr or None, stream or None), "rt_light_hits_mirrored_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,

@@ -1,10 +1,11 @@
 // rt_light.cpp -- rt_hit_surfaces / rt_light_hits, the shadow term's
 // rt_shadow_hits / rt_light_hits_shadowed and the mirror bounce's
 // rt_reflect_hits / rt_light_hits_reflected and the two together,
-// rt_shadow_hits_reflected / rt_light_hits_shadowed_reflected, on the host, and
+// rt_shadow_hits_reflected / rt_light_hits_shadowed_reflected, and the mirror
+// chain's rt_bounce_hits / rt_light_hits_mirrored, on the host, and
 // the argument check they share with the device entry points (the launch of
 // rt_light_device.inc, for rt_light.hip, rt_shadow.hip, rt_reflect.hip and
-// rt_shadow_reflect.hip).  One pixel loop, run(); each function is its
+// rt_shadow_reflect.hip; rt_mirror.hip's own).  One pixel loop, run(); each function is its
 // argument checks and the per-pixel call it hands to the loop.
 // Plain C++, no HIP.  The arithmetic is include/rt_light_impl.h, the text the
 // kernel compiles too; built with -ffp-contract=off like rt_scene.cpp.
@@ -75,6 +76,51 @@ int run(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32_t
 extern "C" {
 
 using namespace rt_light;
+
+// The geometry of one bounce of the mirror chain.
+int rt_bounce_hits(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                   int32_t width, int32_t row_begin, int32_t row_end, int32_t bounce,
+                   rt_hit* out) {
+    if (bounce < 1 || bounce > RT_MAX_BOUNCES) return RT_ERR_INVALID_ARG;
+    return run(hits, scene, ray_dir, width, row_begin, row_end, false, 0, out,
+               [bounce](const auto&... a) {
+                   const Bounce b = bounce_chain_pixel(a..., bounce);
+                   return rt_hit{b.best, b.obj2};
+               });
+}
+
+// The lit frame with a mirror chain and one reflectivity per colour slot.
+int rt_light_hits_mirrored(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
+                           int32_t width, int32_t row_begin, int32_t row_end,
+                           const float* reflectivity, int32_t max_bounces, int32_t shadows,
+                           int32_t out_format, void* out) {
+    if (out_format != RT_FORMAT_I32X4 && out_format != RT_FORMAT_RGBA8) return RT_ERR_INVALID_ARG;
+    if (max_bounces < 0 || max_bounces > RT_MAX_BOUNCES) return RT_ERR_INVALID_ARG;
+    if (shadows != 0 && shadows != 1) return RT_ERR_INVALID_ARG;
+    const int rc = check(hits, scene, ray_dir, width, row_begin, row_end, out);
+    if (rc) return rc;
+    // the array: every value in [0, 1] wherever one is given (NaN is refused
+    // too); it may be missing only where no slot of it can be read
+    const int64_t n_slots = static_cast<int64_t>(scene->num_cubes) + scene->num_spheres;
+    if (!reflectivity && max_bounces > 0 && n_slots > 0) return RT_ERR_INVALID_ARG;
+    bool mirrors = false;
+    if (reflectivity)
+        for (int64_t i = 0; i < n_slots; ++i) {
+            if (!(reflectivity[i] >= 0.0f && reflectivity[i] <= 1.0f)) return RT_ERR_INVALID_ARG;
+            mirrors = mirrors || reflectivity[i] != 0.0f;
+        }
+    if (max_bounces == 0 || !mirrors)  // rt_light_hits' / rt_light_hits_shadowed's frame, no walk
+        return shadows ? rt_light_hits_shadowed(hits, scene, ray_dir, width, row_begin, row_end,
+                                                out_format, out)
+                       : rt_light_hits(hits, scene, ray_dir, width, row_begin, row_end,
+                                       out_format, out);
+    return run(hits, scene, ray_dir, width, row_begin, row_end, false, out_format, out,
+               [=](const auto&... a) {
+                   Lit l;
+                   lit_pixel_mirrored(a..., reflectivity, max_bounces, shadows != 0, l.p);
+                   return l;
+               });
+}
 
 // The mask at the point the bounce meets.
 int rt_shadow_hits_reflected(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],
