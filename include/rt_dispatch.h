@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "rt_hip.h"
+#include "rt_hip_debug.h"
 
 #ifndef RT_BIN_MASKS
 #define RT_BIN_MASKS 1            // default of rt_debug_set_bin_masks
@@ -102,6 +103,29 @@
 
 namespace rt_dispatch {
 
+/* The working set of frame bytes from which the frame stores take
+ * RT_STORE_LARGE (int32x4: nontemporal and written through).  Measured at
+ * both sides of it (profiles/store_policy/README.md): one 256 MiB frame
+ * written over and over loses with them (config 3 on one stream, 50.6 ->
+ * 53.3 us per frame), two such frames in flight gain (45.7 -> 42.7), and so
+ * does one 1 GiB frame (config 4, 193.9 -> 184.6).  512 MiB is where a single
+ * frame already changed sides for nontemporal stores (Knobs::wide_tile_bytes). */
+constexpr int64_t kStoreLargeBytes = (int64_t)1 << 29;
+/* Renders a target stays in the working set for without being written again,
+ * and the entries of the per-device ring (one per render of that window).
+ * Twice the most slots a measured frame loop uses (the RGBA8 leg's 4,
+ * DESIGN.md section 3.4), so every buffer of such a loop stays in it; loops of
+ * 2 and 4 slots were measured with it. */
+constexpr int kTargetWindow = 8;
+
+/* Record a render of `bytes` bytes at `base` on `device` and return the
+ * device's working set: the bytes of the union of the distinct targets of its
+ * last kTargetWindow renders, by any context of the process (this one
+ * included).  Thread-safe. */
+int64_t track_target(int device, const void* base, int64_t bytes);
+/* Forget every device's targets (tests). */
+void reset_targets();
+
 /* What one tile build (one inclusion of rt_trace.inc) contributes to the
  * policy: its coarse-bin shape, its kernels' capacities and the sizes of the
  * records its prep writes. */
@@ -168,6 +192,11 @@ struct Knobs {
     // 8-rank band, config 4's half frame, a 512 MiB Texture; measured with 64x4
     // tiles), 384 MiB and smaller ones from 16x16.
     int64_t wide_tile_bytes = (int64_t)1 << 29;
+    // The frame stores' cache policy (rt_debug_set_store_policy): RT_STORE_AUTO
+    // = RT_STORE_LARGE once the frames in flight on the device (track_target)
+    // reach store_large_bytes, else RT_STORE_DEFAULT.
+    int store_policy = RT_STORE_AUTO;
+    int64_t store_large_bytes = kStoreLargeBytes;
 };
 
 /* rt_debug_set_tile_variant: 0 = by frame size, 1 = 16x16, 2 = wide (128x2) */
@@ -215,16 +244,26 @@ struct Decision {
      * od_hi: 2 below it, 3 above) */
     unsigned long long area_units, od_min, od_lo, od_hi;
     bool feeds_overdraw;  /* prep sums the box overdraw: the launch takes an overdraw slot */
+    /* the frame stores' cache policy (RT_STORE_*), in the chains whose trace
+     * has one: RT_KERNEL_TRACE_BIN, RT_KERNEL_TRACE_SPLIT, RT_KERNEL_TRACE */
+    int store_policy;
 };
+
+/* The store policy of a frame of `frame_bytes` bytes while the device writes
+ * a working set of `working_set` bytes (track_target; a working set below the
+ * frame's own size, 0 for one, means the frame alone).  `verdict`: choose()'s;
+ * nearly empty frames (verdict 1) keep RT_STORE_DEFAULT. */
+int store_policy_of(const Knobs& k, int64_t frame_bytes, int64_t working_set, unsigned verdict);
 
 /* The dispatch policy.  `verdict`: the context's overdraw verdict word as the
  * caller read it (0 = none yet); `trace_mode`: the diagnostics builds' trace
- * ablation (0 = none).  Returns RT_OK and *out, RT_ERR_UNSUPPORTED
+ * ablation (0 = none); `working_set`: track_target()'s answer for the frame
+ * this launch writes (0: the launch's own bytes).  Returns RT_OK and *out, RT_ERR_UNSUPPORTED
  * (RT_PATH_BINNED for rays the binned path cannot take) or RT_ERR_INVALID_ARG
  * (a band whose trace grid would pass 32 bits). */
 int choose(const Geometry& g, const Knobs& k, int n_cu, int32_t fmt, int n_spheres, int n_cubes,
            int32_t width, int32_t rows, bool can_bin, int32_t path, unsigned verdict,
-           int trace_mode, Decision* out);
+           int trace_mode, Decision* out, int64_t working_set = 0);
 
 }  // namespace rt_dispatch
 

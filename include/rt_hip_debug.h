@@ -90,6 +90,28 @@ int rt_debug_set_trace_bin(rt_ctx* ctx, int mode);
  * only way).  RT_ERR_UNSUPPORTED for 0 where the word is not mapped. */
 int rt_debug_set_verdict_copy(rt_ctx* ctx, int copy);
 
+/* The cache policy of the frame stores of trace_bin_kernel, trace3_kernel and
+ * trace3_split_kernel.  The library keeps, per device, the distinct frame
+ * targets (base, bytes) of the process's last 8 renders; their union is the
+ * working set the GPU is writing.  RT_STORE_DEFAULT: the tile build's own
+ * choice per format; RT_STORE_LARGE: nontemporal stores in every format,
+ * int32x4 frames' written through as well (nt sc1), taken once the working
+ * set reaches 512 MiB (one frame of that size, or several smaller ones in
+ * flight) unless the frame is nearly empty (box overdraw below one frame). */
+enum {
+    RT_STORE_AUTO = -1,    /* rt_debug_set_store_policy only: by working set */
+    RT_STORE_DEFAULT = 0,
+    RT_STORE_LARGE = 1
+};
+/* Force a store policy on this context's renders (RT_STORE_AUTO: the default). */
+int rt_debug_set_store_policy(rt_ctx* ctx, int policy);
+/* The working set, in bytes, from which RT_STORE_AUTO takes RT_STORE_LARGE
+ * (0 restores the default, 512 MiB). */
+int rt_debug_set_store_large_bytes(rt_ctx* ctx, int64_t bytes);
+/* The store policy of the last render enqueued on this context
+ * (RT_STORE_DEFAULT where the kernel that ran has only one). */
+int rt_debug_last_store_policy(rt_ctx* ctx, int32_t* policy);
+
 /* The box overdraw of the last binned render of >= 1 band on this context
  * (prep's sum of the primitives' pixel-box areas over the band's area, in
  * frames; what the automatic path choices gate on).  Synchronises the

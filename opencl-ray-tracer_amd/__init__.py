@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = (
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
                 4: "generic_kernel", 5: "trace3_split_kernel", 6: "trace_bin_kernel"}
+# the frame stores' cache policies (RT_STORE_*, rt_hip_debug.h) by name
+STORE_POLICIES = {"auto": -1, "default": 0, "large": 1}
 # exported only by the diagnostics build (make RT_DIAG=1, include/rt_hip_diag.h)
 DIAG_SYMBOLS = ("rt_debug_set_trace_mode",)
 
@@ -226,6 +228,9 @@ def library() -> ctypes.CDLL:
         "rt_debug_set_trace_bin": (ctypes.c_int, [vp, ctypes.c_int]),
         "rt_debug_set_verdict_copy": (ctypes.c_int, [vp, ctypes.c_int]),
         "rt_debug_last_overdraw": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
+        "rt_debug_set_store_policy": (ctypes.c_int, [vp, ctypes.c_int]),
+        "rt_debug_set_store_large_bytes": (ctypes.c_int, [vp, ctypes.c_int64]),
+        "rt_debug_last_store_policy": (ctypes.c_int, [vp, ctypes.POINTER(i32)]),
         "rt_debug_triangle_t_bounds": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32,
                                                       i32, i32, vp]),
         "rt_debug_triangle_box_wide": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
@@ -992,6 +997,27 @@ class RayTracer:
         True = a copy every 8th binned launch (the fallback; tests)."""
         _check(library().rt_debug_set_verdict_copy(self._ctx, int(bool(copy))),
                "rt_debug_set_verdict_copy")
+
+    def store_policy(self, policy="auto", large_bytes: int = 0) -> None:
+        """Diagnostics: the frame stores' cache policy of the binned trace
+        kernels (rt_debug_set_store_policy): "auto" (default) = "large"
+        (nontemporal stores) once the distinct frames the process rendered
+        to on this device in its last 8 renders reach `large_bytes`
+        (rt_debug_set_store_large_bytes; 0 = the default, 512 MiB), else
+        "default"; or either one forced."""
+        lib = library()
+        _check(lib.rt_debug_set_store_policy(self._ctx, STORE_POLICIES.get(policy, policy)),
+               "rt_debug_set_store_policy")
+        _check(lib.rt_debug_set_store_large_bytes(self._ctx, int(large_bytes)),
+               "rt_debug_set_store_large_bytes")
+
+    def last_store_policy(self) -> str:
+        """rt_debug_last_store_policy: "default" or "large", the store policy
+        of the last render enqueued on this context."""
+        k = ctypes.c_int32()
+        _check(library().rt_debug_last_store_policy(self._ctx, ctypes.byref(k)),
+               "rt_debug_last_store_policy")
+        return {v: n for n, v in STORE_POLICIES.items()}.get(k.value, k.value)
 
     def last_overdraw(self) -> float:
         """rt_debug_last_overdraw: the last binned render's box overdraw, in

@@ -111,6 +111,11 @@ struct rt_ctx {
     int trace_mode = 0;  // diagnostics ablation (RT_DIAG builds), see trace3_kernel
     int last_kernel = RT_KERNEL_NONE;  // the dominant kernel of the last launch (rt_last_kernel)
     int n_cu = 256;  // compute units (rt_init)
+    // the frame bytes the device is writing (rt_dispatch::track_target, taken
+    // by render_launch for the render it enqueues), and the store policy
+    // chosen from them (rt_debug_last_store_policy)
+    int64_t working_set = 0;
+    int last_store_policy = RT_STORE_DEFAULT;
     // the dispatch policy's tunables (rt_dispatch.h; the rt_debug_set_* functions)
     rt_dispatch::Knobs knobs;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -289,6 +294,9 @@ __global__ void __launch_bounds__(256) grid_check_kernel(const float4* __restric
 int render_launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origins,
                   int32_t width, int32_t row_begin, int32_t row_end, int32_t fmt, int32_t path,
                   void* out, hipStream_t stream, int32_t* used_path) {
+    ctx->working_set = rt_dispatch::track_target(
+        ctx->device, out, (int64_t)rt_args::frame_bytes(width, row_end - row_begin, fmt));
+    ctx->last_store_policy = RT_STORE_DEFAULT;
     return rt_dispatch::use_wide_tiles(ctx->knobs, width, row_end - row_begin, fmt)
                ? wide::launch(ctx, s, d, origins, width, row_begin, row_end, fmt, path, out,
                               stream, used_path)
@@ -939,6 +947,24 @@ int rt_debug_last_overdraw(rt_ctx* ctx, double* frames) {
 int rt_debug_set_trace_bin(rt_ctx* ctx, int mode) {
     if (!ctx || mode < 0 || mode > 2) return RT_ERR_INVALID_ARG;
     ctx->knobs.trace_bin = mode;
+    return RT_OK;
+}
+
+int rt_debug_set_store_policy(rt_ctx* ctx, int policy) {
+    if (!ctx || policy < RT_STORE_AUTO || policy > RT_STORE_LARGE) return RT_ERR_INVALID_ARG;
+    ctx->knobs.store_policy = policy;
+    return RT_OK;
+}
+
+int rt_debug_set_store_large_bytes(rt_ctx* ctx, int64_t bytes) {
+    if (!ctx || bytes < 0) return RT_ERR_INVALID_ARG;
+    ctx->knobs.store_large_bytes = bytes ? bytes : rt_dispatch::Knobs{}.store_large_bytes;
+    return RT_OK;
+}
+
+int rt_debug_last_store_policy(rt_ctx* ctx, int32_t* policy) {
+    if (!ctx || !policy) return RT_ERR_INVALID_ARG;
+    *policy = ctx->last_store_policy;
     return RT_OK;
 }
 

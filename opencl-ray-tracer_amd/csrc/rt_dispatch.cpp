@@ -6,6 +6,9 @@
 #include "rt_dispatch.h"
 
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #include "rt_args.h"
 
@@ -43,7 +46,72 @@ FormatGates gates_of(const Knobs& k, int32_t fmt) {
     return {k.coarse_cull_tri, k.coarse_cull_overdraw, 2u};
 }
 
+// The frame targets of one device's recent renders: a ring with one entry
+// per render of the window, so a target written within it always has one.
+struct Target {
+    uintptr_t base = 0;
+    int64_t bytes = 0;
+    uint64_t launch = 0;  // the device's render count when last written (0: empty)
+};
+struct DeviceTargets {
+    Target ring[kTargetWindow];
+    uint64_t launches = 0;
+};
+std::mutex g_targets_mu;
+std::map<int, DeviceTargets> g_targets;
+
 }  // namespace
+
+int64_t track_target(int device, const void* base, int64_t bytes) {
+    std::lock_guard<std::mutex> lock(g_targets_mu);
+    DeviceTargets& d = g_targets[device];
+    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+    const uint64_t now = ++d.launches;
+    // the same target again refreshes its entry; a new one takes the oldest
+    Target* slot = &d.ring[0];
+    for (Target& t : d.ring) {
+        if (t.launch && t.base == b && t.bytes == bytes) {
+            slot = &t;
+            break;
+        }
+        if (t.launch < slot->launch) slot = &t;
+    }
+    *slot = Target{b, bytes, now};
+    // the union of the ranges written during the window: sorted by base,
+    // each range counts what lies past the end of those before it
+    std::pair<uintptr_t, uintptr_t> live[kTargetWindow];
+    int n = 0;
+    for (const Target& t : d.ring)
+        if (t.launch && now - t.launch < (uint64_t)kTargetWindow && t.bytes > 0)
+            live[n++] = {t.base, t.base + (uintptr_t)t.bytes};
+    std::sort(live, live + n);
+    int64_t sum = 0;
+    uintptr_t end = 0;
+    for (int i = 0; i < n; ++i) {
+        const uintptr_t from = std::max(live[i].first, end);
+        if (live[i].second > from) sum += (int64_t)(live[i].second - from);
+        end = std::max(end, live[i].second);
+    }
+    return sum;
+}
+
+void reset_targets() {
+    std::lock_guard<std::mutex> lock(g_targets_mu);
+    g_targets.clear();
+}
+
+int store_policy_of(const Knobs& k, int64_t frame_bytes, int64_t working_set, unsigned verdict) {
+    if (k.store_policy != RT_STORE_AUTO) return k.store_policy;
+    // Frames with next to nothing in them (overdraw verdict 1: the boxes cover
+    // less than a frame) keep the default: nearly every wave stores at once,
+    // and the written-through stores then gain nothing that holds from one
+    // machine to the next (config 3's sparse scene, 2 frames in flight, 600
+    // frames: 46.1 -> 46.9 us per frame on one, 43.9 -> 43.7 on another;
+    // profiles/store_policy/README.md).
+    return verdict != 1u && std::max(frame_bytes, working_set) >= k.store_large_bytes
+               ? RT_STORE_LARGE
+               : RT_STORE_DEFAULT;
+}
 
 bool use_wide_tiles(const Knobs& k, int32_t width, int32_t rows, int32_t fmt) {
     const int64_t bytes = (int64_t)width * rows * (int64_t)rt_args::pixel_bytes(fmt);
@@ -88,11 +156,14 @@ int64_t band_rows_of(const Geometry& g, const Knobs& k, int64_t n_prims, int32_t
 
 int choose(const Geometry& g, const Knobs& k, int n_cu, int32_t fmt, int n_spheres, int n_cubes,
            int32_t width, int32_t rows, bool can_bin, int32_t path, unsigned verdict,
-           int trace_mode, Decision* out) {
+           int trace_mode, Decision* out, int64_t working_set) {
     Decision& dc = *out;
     dc = Decision{};
     dc.band_rows = rows;
     dc.split = dc.coarse_waves = 1;
+    dc.store_policy = RT_STORE_DEFAULT;
+    const int store_policy = store_policy_of(
+        k, (int64_t)width * rows * (int64_t)rt_args::pixel_bytes(fmt), working_set, verdict);
     if (path == RT_PATH_BINNED && !can_bin) return RT_ERR_UNSUPPORTED;
     if (!(path == RT_PATH_BINNED || (path == RT_PATH_AUTO && can_bin))) {
         dc.chain = RT_KERNEL_GENERIC;  // explicit origins / other directions: brute force
@@ -148,6 +219,7 @@ int choose(const Geometry& g, const Knobs& k, int n_cu, int32_t fmt, int n_spher
                     verdict >= 1u && verdict <= gates.bin_verdict_max))) {
         dc.chain = RT_KERNEL_TRACE_BIN;
         dc.feeds_overdraw = true;
+        dc.store_policy = store_policy;
         return RT_OK;
     }
     if (n_prims > 0) {
@@ -177,6 +249,7 @@ int choose(const Geometry& g, const Knobs& k, int n_cu, int32_t fmt, int n_spher
                : n_tiles <= k.split2_tiles ? 2
                                            : 1;
     dc.chain = dc.split > 1 ? RT_KERNEL_TRACE_SPLIT : RT_KERNEL_TRACE;
+    dc.store_policy = store_policy;
     return RT_OK;
 }
 

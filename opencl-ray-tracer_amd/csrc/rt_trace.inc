@@ -1024,20 +1024,39 @@ constexpr bool kNtRgba8 = (RT_NT_STORES & 2) != 0;
 // RT_FORMAT_HIT frames (8-byte pixels): bit 2 (DESIGN.md §3.5)
 constexpr bool kNtHit = (RT_NT_STORES & 4) != 0;
 typedef unsigned uint2v __attribute__((ext_vector_type(2)));
+// The cache-policy bits (the raw buffer store's aux operand on gfx950: bit 0
+// sc0, bit 1 nt, bit 4 sc1) of a format's frame stores under a store policy
+// (rt_dispatch.h: RT_STORE_DEFAULT = this build's choice above,
+// RT_STORE_LARGE = the frames in flight have outgrown what the last-level
+// cache absorbs).  Under RT_STORE_LARGE int32x4 frames are stored nt sc1,
+// nontemporal and written through, so no dirty line stays behind in an L2 for
+// a later store to push out: of the eight combinations of the three bits it
+// and nt sc0 sc1 alone gain in the two-buffer frame loop (config 3, 2 frames
+// in flight: 45.7 -> 42.7 us per frame, nt alone 45.6; config 4's one 1 GiB
+// frame 193.9 -> 184.6, nt alone the same 194.0), and on one 256 MiB buffer
+// written over and over it loses (50.6 -> 53.3), hence the policy
+// (profiles/store_policy/README.md).  RGBA8 frames measured fastest with nt
+// alone (4 in flight: nt 25.8, nt sc1 26.5, plain 27.9) and HIT frames keep
+// it.  Two policies with equal bits share one kernel instance.
+constexpr int kAuxNt = 2, kAuxSc1 = 16;
+constexpr int store_aux(int fmt, int policy) {
+    return policy == RT_STORE_LARGE
+               ? (fmt == RT_FORMAT_I32X4 ? kAuxNt | kAuxSc1 : kAuxNt)
+           : (fmt == RT_FORMAT_I32X4 ? kNtI32 : fmt == RT_FORMAT_HIT ? kNtHit : kNtRgba8) ? kAuxNt
+                                                                                          : 0;
+}
 // (raw buffer stores: the tile origin in a buffer descriptor, the lane's
-// 32-bit byte offset in a VGPR, the row's byte step as the scalar offset;
-// aux bit 1 is nt on gfx950, the same bit __builtin_nontemporal_store sets)
-template <int kFmt>
+// 32-bit byte offset in a VGPR, the row's byte step as the scalar offset)
+template <int kFmt, int kAux>
 __device__ __forceinline__ void store_shaded(__amdgpu_buffer_rsrc_t tile, unsigned lane_off,
                                              int row_off, int4v pix) {
     if (kFmt == RT_FORMAT_I32X4)
-        __builtin_amdgcn_raw_buffer_store_b128(pix, tile, (int)lane_off, row_off, kNtI32 ? 2 : 0);
+        __builtin_amdgcn_raw_buffer_store_b128(pix, tile, (int)lane_off, row_off, kAux);
     else if (kFmt == RT_FORMAT_HIT)
         __builtin_amdgcn_raw_buffer_store_b64(uint2v{(unsigned)pix.x, (unsigned)pix.y}, tile,
-                                              (int)lane_off, row_off, kNtHit ? 2 : 0);
+                                              (int)lane_off, row_off, kAux);
     else
-        __builtin_amdgcn_raw_buffer_store_b32(pix.x, tile, (int)lane_off, row_off,
-                                              kNtRgba8 ? 2 : 0);
+        __builtin_amdgcn_raw_buffer_store_b32(pix.x, tile, (int)lane_off, row_off, kAux);
 }
 
 // The Texture packing (MainState.cpp:1026-1036) of three (int) channels.
@@ -1164,7 +1183,7 @@ __device__ __forceinline__ void shade_pixels(const float4* __restrict__ colours,
 // stores take the saddr + voffset form with no per-pixel 64-bit address
 // arithmetic (round 4).  `full`: the whole tile lies inside the frame band,
 // so no per-lane bounds checks.
-template <int kMode, int kFmt>
+template <int kMode, int kFmt, int kAux = store_aux(kFmt, RT_STORE_DEFAULT)>
 __device__ __forceinline__ void store_rows(const int4v* pix, int rel_x, int rel_y, int lane,
                                            int width, int band_h, bool full,
                                            void* __restrict__ out) {
@@ -1184,7 +1203,7 @@ __device__ __forceinline__ void store_rows(const int4v* pix, int rel_x, int rel_
         const bool store = kMode != 3 || pix[j].x == 0x7fffffff;
         const int row_off = (pix_dy(j) * width + pix_dx(j)) * kBytes;
         const bool in = full || (rel_x + lx + pix_dx(j) < width && rel_y + ly + pix_dy(j) < band_h);
-        if (in && store) store_shaded<kFmt>(tile, lane_off, row_off, pix[j]);
+        if (in && store) store_shaded<kFmt, kAux>(tile, lane_off, row_off, pix[j]);
     }
 }
 
@@ -1771,7 +1790,7 @@ static_assert((kTiles & (kTiles - 1)) == 0, "tiles per bin: a power of two");
 // preloading the first 14 dwords arrive in SGPRs.)
 // Every output format is an instance of this one template; kMode != 0 (the
 // trace ablations of rt_debug_set_trace_mode) exists in RT_DIAG builds only.
-template <int kMode, int kFmt>
+template <int kMode, int kFmt, int kAux>
 __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_kernel(
     const int* __restrict__ counts, const int* __restrict__ lists,
     const TriRec* __restrict__ tri, const SphRec* __restrict__ sph, int n_cx, int half_cap,
@@ -1894,7 +1913,8 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_kernel(
 #endif
         shade_pixels<kMode, kFmt>(colours, closest, hit, pix);
         const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
-        store_rows<kMode, kFmt>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
+        store_rows<kMode, kFmt, kAux>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full,
+                                      out);
     }  // finite scene, tile inside the frame
 #if RT_TIMELINE
     {
@@ -1928,7 +1948,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_kernel(
 // cull uses its own closest values, which bound the tile's from above, so
 // it skips no sphere the sequential walk would have taken.
 constexpr int kSplitMax = 4;  // waves per tile (workgroup of 256 lanes; 8 measured slower)
-template <int kFmt>
+template <int kFmt, int kAux>
 __global__ void __launch_bounds__(64 * kSplitMax) RT_TRACE_ATTR trace3_split_kernel(
     SceneDev scene, const TriRec* __restrict__ tri, const SphRec* __restrict__ sph,
     const float4* __restrict__ colours, const int* __restrict__ counts,
@@ -2048,7 +2068,7 @@ __global__ void __launch_bounds__(64 * kSplitMax) RT_TRACE_ATTR trace3_split_ker
     int4v pix[kRowsPerLane];
     shade_pixels<0, kFmt>(colours, closest, hit, pix);
     const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
-    store_rows<0, kFmt>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
+    store_rows<0, kFmt, kAux>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
 }
 
 
@@ -2202,7 +2222,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
 // sphere cull stays.  Non-finite scene data: the reference verbatim.
 constexpr int kBinCap = 1024;  // trace_bin_kernel: scenes of at most this many primitives
 
-template <int kFmt>
+template <int kFmt, int kAux>
 __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
     // (the first 14 argument dwords arrive preloaded in SGPRs: the ones a
     // wave needs before its first data loads; the rest load in their shadow)
@@ -2347,7 +2367,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
     int4v pix[kRowsPerLane];
     shade_pixels<0, kFmt>(colours, closest, hit, pix);
     const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
-    store_rows<0, kFmt>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
+    store_rows<0, kFmt, kAux>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
 }
 
 
@@ -2553,6 +2573,20 @@ int preload_one(K kernel) {
     one(preload_one(KERNEL<RT_FORMAT_I32X4, ##__VA_ARGS__>));     \
     one(preload_one(KERNEL<RT_FORMAT_RGBA8, ##__VA_ARGS__>));     \
     one(preload_one(KERNEL<RT_FORMAT_HIT, ##__VA_ARGS__>))
+// The kernels that write whole frames on the binned path, by format and the
+// store policy's cache bits (trace3_kernel's as <format, bits, mode>).
+template <int kFmt, int kAux, int kMode = 0>
+constexpr auto trace3_of = trace3_kernel<kMode, kFmt, kAux>;
+// every format's instances of KERNEL<format, bits of each store policy>
+#undef RT_PRELOAD_STORES
+#define RT_PRELOAD_STORES(KERNEL)                                                \
+    RT_PRELOAD_FMTS_AUX(KERNEL, RT_STORE_DEFAULT);                               \
+    RT_PRELOAD_FMTS_AUX(KERNEL, RT_STORE_LARGE)
+#undef RT_PRELOAD_FMTS_AUX
+#define RT_PRELOAD_FMTS_AUX(KERNEL, POLICY)                                              \
+    one(preload_one(KERNEL<RT_FORMAT_I32X4, store_aux(RT_FORMAT_I32X4, POLICY)>));       \
+    one(preload_one(KERNEL<RT_FORMAT_RGBA8, store_aux(RT_FORMAT_RGBA8, POLICY)>));       \
+    one(preload_one(KERNEL<RT_FORMAT_HIT, store_aux(RT_FORMAT_HIT, POLICY)>))
 int preload() {
     int rc = RT_OK;
     auto one = [&rc](int r) { if (r != RT_OK) rc = r; };
@@ -2562,11 +2596,9 @@ int preload() {
     one(preload_one(coarse3_kernel<2>));
     one(preload_one(coarse3_kernel<4>));
     one(preload_one(coarse3_kernel<8>));
-    one(preload_one(trace3_kernel<0, RT_FORMAT_I32X4>));
-    one(preload_one(trace3_kernel<0, RT_FORMAT_RGBA8>));
-    one(preload_one(trace3_kernel<0, RT_FORMAT_HIT>));
-    RT_PRELOAD_FMTS(trace3_split_kernel);
-    RT_PRELOAD_FMTS(trace_bin_kernel);
+    RT_PRELOAD_STORES(trace3_of);
+    RT_PRELOAD_STORES(trace3_split_kernel);
+    RT_PRELOAD_STORES(trace_bin_kernel);
     RT_PRELOAD_FMTS(trace_small_kernel, 1);
     RT_PRELOAD_FMTS(trace_small_kernel, 2);
     RT_PRELOAD_FMTS(trace_small_kernel, 4);
@@ -2608,11 +2640,20 @@ int copy_verdict(rt_ctx* ctx, hipStream_t stream) {
     (fmt == RT_FORMAT_I32X4 ? KERNEL<RT_FORMAT_I32X4, ##__VA_ARGS__>  \
      : fmt == RT_FORMAT_HIT ? KERNEL<RT_FORMAT_HIT, ##__VA_ARGS__>    \
                             : KERNEL<RT_FORMAT_RGBA8, ##__VA_ARGS__>)
+// KERNEL<format, the cache bits of the band's store policy, ...> (the frame
+// writers of the binned path; dc.store_policy is rt_dispatch::choose()'s)
+#undef RT_BY_STORE
+#define RT_BY_STORE(KERNEL, FMT, ...)                                            \
+    (b.dc.store_policy == RT_STORE_LARGE                                         \
+         ? KERNEL<FMT, store_aux(FMT, RT_STORE_LARGE), ##__VA_ARGS__>            \
+         : KERNEL<FMT, store_aux(FMT, RT_STORE_DEFAULT), ##__VA_ARGS__>)
+#undef RT_BY_FMT_STORE
+#define RT_BY_FMT_STORE(KERNEL, ...)                                                \
+    (fmt == RT_FORMAT_I32X4 ? RT_BY_STORE(KERNEL, RT_FORMAT_I32X4, ##__VA_ARGS__)   \
+     : fmt == RT_FORMAT_HIT ? RT_BY_STORE(KERNEL, RT_FORMAT_HIT, ##__VA_ARGS__)     \
+                            : RT_BY_STORE(KERNEL, RT_FORMAT_RGBA8, ##__VA_ARGS__))
 #undef RT_TRACE3_BY_FMT
-#define RT_TRACE3_BY_FMT(MODE)                                     \
-    (fmt == RT_FORMAT_I32X4 ? trace3_kernel<MODE, RT_FORMAT_I32X4> \
-     : fmt == RT_FORMAT_HIT ? trace3_kernel<MODE, RT_FORMAT_HIT>   \
-                            : trace3_kernel<MODE, RT_FORMAT_RGBA8>)
+#define RT_TRACE3_BY_FMT(MODE) RT_BY_FMT_STORE(trace3_of, MODE)
 #ifndef RT_SKIP_DIAG
 #define RT_SKIP_DIAG 0  // diagnostics (RT_DIAG builds): after a context's first 16 binned launches skip prep (1) / coarse (2)
 #endif
@@ -2738,7 +2779,7 @@ int enqueue_trace_bin(const Band& b) {
     const OdSlots od = take_od_slots(ctx, b.dc.area_units);
     int rc;
     if ((rc = enqueue_prep(b, od.word)) || (rc = skip_k(ctx, b.pe_coarse))) return rc;
-    auto bk = RT_BY_FMT(trace_bin_kernel);
+    auto bk = RT_BY_FMT_STORE(trace_bin_kernel);
     ctx->last_kernel = RT_KERNEL_TRACE_BIN;
     rc = launch_k(bk, dim3((unsigned)(pl.n_cx * kTiles), (unsigned)pl.n_cy), dim3(64), b.stream,
                   kernel_events(ctx, b.pe_trace, true, true), pl.n_chunks, b.width, b.row_begin,
@@ -2795,7 +2836,7 @@ int enqueue_coarse(const Band& b) {
     const dim3 trace_grid((unsigned)(pl.n_cx * kTiles), (unsigned)pl.n_cy);
     ctx->last_kernel = dc.chain;
     if (dc.chain == RT_KERNEL_TRACE_SPLIT) {
-        auto sk = RT_BY_FMT(trace3_split_kernel);
+        auto sk = RT_BY_FMT_STORE(trace3_split_kernel);
         rc = launch_k(sk, trace_grid, dim3(64 * dc.split), b.stream,
                       kernel_events(ctx, b.pe_trace, true, true), b.sd, (const TriRec*)ws.tri,
                       (const SphRec*)ws.sph, (const float4*)ws.colours, (const int*)ws.counts,
@@ -2833,8 +2874,9 @@ int launch(rt_ctx* ctx, const rt_scene* s, const float d[4], const float* origin
     rt_dispatch::Decision dc;
     int rc = rt_dispatch::choose(kGeometry, ctx->knobs, ctx->n_cu, fmt, s->num_spheres,
                                  s->num_cubes, width, rows, binned_ok(d, origins), path, verdict,
-                                 ctx->trace_mode, &dc);
+                                 ctx->trace_mode, &dc, ctx->working_set);
     if (rc) return rc;
+    if (dc.chain != RT_KERNEL_NONE) ctx->last_store_policy = dc.store_policy;
     if (used_path) *used_path = dc.chain == RT_KERNEL_GENERIC ? RT_PATH_GENERIC : RT_PATH_BINNED;
     if (dc.band_rows < rows) {
         // internal bands, each a band render, in order on the same stream
