@@ -1,5 +1,5 @@
 // light_args_check.cpp -- rt_hit_surfaces / rt_light_hits (csrc/rt_light.cpp
-// with csrc/rt_args.cpp) as a stand-alone program like hit_args_check.cpp:
+// with csrc/rt_args.cpp) as a stand-alone program on tests/light_check.h:
 // tests/test_light_hits.py builds it with -fsanitize=address,undefined and
 // runs it.  No GPU.
 //
@@ -11,28 +11,11 @@
 //     cube face seen head on, a foreign t;
 //   - the argument checks.
 // Exit 0 and "light args check ok" on success.
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <memory>
+#include "light_check.h"
 
-#include "rt_hip.h"
+using namespace light_check;
 
 namespace {
-
-int failures = 0;
-
-#define CHECK(cond)                                                              \
-    do {                                                                         \
-        if (!(cond)) {                                                           \
-            std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, \
-                         #cond);                                                 \
-            ++failures;                                                          \
-        }                                                                        \
-    } while (0)
-
-const float kDir[4] = {0.0f, 0.0f, -1.0f, -1.0f};
-const int32_t kBlack[4] = {0, 0, 0, 255};
 
 bool is_zero_surface(const rt_surface& s) {
     return s.nx == 0.0f && s.ny == 0.0f && s.nz == 0.0f && s.triangle == -1;
@@ -43,47 +26,13 @@ bool is_zero_surface(const rt_surface& s) {
 int main() {
     static_assert(sizeof(rt_surface) == 16, "four 32-bit words per pixel");
 
-    // ---- an empty scene with NULL arrays: every pixel a miss -------------
-    {
-        rt_scene empty{};
-        const int w = 5, rows = 3;
-        std::unique_ptr<rt_hit[]> hits(new rt_hit[w * rows]);
-        for (int i = 0; i < w * rows; ++i) hits[i] = rt_hit{300000.0f, -1};
-        std::unique_ptr<rt_surface[]> surf(new rt_surface[w * rows]);
-        std::unique_ptr<int32_t[]> px(new int32_t[4 * w * rows]);
-        std::unique_ptr<uint32_t[]> words(new uint32_t[w * rows]);
-        CHECK(rt_hit_surfaces(hits.get(), &empty, kDir, w, 0, rows, surf.get()) == RT_OK);
-        CHECK(rt_light_hits(hits.get(), &empty, kDir, w, 0, rows, RT_FORMAT_I32X4, px.get()) ==
-              RT_OK);
-        CHECK(rt_light_hits(hits.get(), &empty, kDir, w, 0, rows, RT_FORMAT_RGBA8, words.get()) ==
-              RT_OK);
-        for (int i = 0; i < w * rows; ++i) {
-            CHECK(is_zero_surface(surf[i]));
-            CHECK(std::memcmp(&px[4 * i], kBlack, sizeof kBlack) == 0);
-            CHECK(words[i] == 0xFF000000u);
-        }
-        // any object is out of range in an empty scene
-        hits[w * rows - 1].object = 0;
-        CHECK(rt_hit_surfaces(hits.get(), &empty, kDir, w, 0, rows, surf.get()) ==
-              RT_ERR_INVALID_ARG);
-        CHECK(rt_light_hits(hits.get(), &empty, kDir, w, 0, rows, RT_FORMAT_I32X4, px.get()) ==
-              RT_ERR_INVALID_ARG);
-    }
-
     // ---- one cube (slot 0), one sphere (slot 1), one light -----------------
     // the cube: x, y in [0, 8], z in [-60, -40]; two triangles per face, only
     // the front face (z = -40) matters for rays along -z
     std::unique_ptr<float[]> verts(new float[144]);
     {
         const float lo[3] = {0.0f, 0.0f, -60.0f}, hi[3] = {8.0f, 8.0f, -40.0f};
-        // corner bit0 = x, bit1 = y, bit2 = z (set = hi), Cube.cpp's order
-        const unsigned char corners[36] = {0, 4, 6, 3, 0, 2, 5, 0, 1, 3, 1, 0, 0, 6, 2, 5, 4, 0,
-                                           6, 4, 5, 7, 1, 3, 1, 7, 5, 7, 3, 2, 7, 2, 6, 7, 6, 5};
-        for (int k = 0; k < 36; ++k) {
-            for (int a = 0; a < 3; ++a)
-                verts[4 * k + a] = (corners[k] >> a & 1u) ? hi[a] : lo[a];
-            verts[4 * k + 3] = 1.0f;
-        }
+        box(verts.get(), lo, hi);
     }
     std::unique_ptr<float[]> cube_col(new float[4]{1.0f, 0.5f, 0.25f, 255.0f});
     std::unique_ptr<float[]> sph_org(new float[4]{32.0f, 24.0f, -50.0f, 1.0f});
@@ -162,39 +111,22 @@ int main() {
     }
 
     // ---- arguments -------------------------------------------------------------
+    auto own = [](const Call& c) {
+        return rt_hit_surfaces(c.hits, c.scene, c.dir, c.w, c.rb, c.re, (rt_surface*)c.out);
+    };
+    auto lit = [](const Call& c, int32_t fmt) {
+        return rt_light_hits(c.hits, c.scene, c.dir, c.w, c.rb, c.re, fmt, c.out);
+    };
     {
         std::unique_ptr<rt_hit[]> hits(new rt_hit[4]{{300000.0f, -1}, {50.0f, 1}, {50.0f, 0},
                                                      {300000.0f, -1}});
         std::unique_ptr<rt_surface[]> surf(new rt_surface[4]);
         std::unique_ptr<int32_t[]> px(new int32_t[16]);
-        CHECK(rt_light_hits(hits.get(), &s, kDir, 2, 0, 2, RT_FORMAT_I32X4, px.get()) == RT_OK);
-        for (int32_t fmt : {2, (int32_t)RT_FORMAT_HIT, 4, -1})
-            CHECK(rt_light_hits(hits.get(), &s, kDir, 2, 0, 2, fmt, px.get()) ==
-                  RT_ERR_INVALID_ARG);
-        CHECK(rt_light_hits(nullptr, &s, kDir, 2, 0, 2, 0, px.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_light_hits(hits.get(), nullptr, kDir, 2, 0, 2, 0, px.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_light_hits(hits.get(), &s, nullptr, 2, 0, 2, 0, px.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_light_hits(hits.get(), &s, kDir, 2, 0, 2, 0, nullptr) == RT_ERR_INVALID_ARG);
-        CHECK(rt_hit_surfaces(hits.get(), &s, kDir, 2, 0, 2, nullptr) == RT_ERR_INVALID_ARG);
-        CHECK(rt_hit_surfaces(hits.get(), &s, kDir, 0, 0, 2, surf.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_hit_surfaces(hits.get(), &s, kDir, 2, -1, 1, surf.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_hit_surfaces(hits.get(), &s, kDir, 2, 2, 2, surf.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_hit_surfaces(hits.get(), &s, kDir, (1 << 24) + 1, 0, 1, surf.get()) ==
-              RT_ERR_INVALID_ARG);
-        rt_scene bad = s;
-        bad.lights = nullptr;
-        CHECK(rt_light_hits(hits.get(), &bad, kDir, 2, 0, 2, 0, px.get()) == RT_ERR_INVALID_ARG);
-        bad = s;
-        bad.num_lights = -1;
-        CHECK(rt_light_hits(hits.get(), &bad, kDir, 2, 0, 2, 0, px.get()) == RT_ERR_INVALID_ARG);
-        for (int32_t obj : {2, -2, INT32_MAX, INT32_MIN}) {
-            hits[3].object = obj;
-            CHECK(rt_hit_surfaces(hits.get(), &s, kDir, 2, 0, 2, surf.get()) ==
-                  RT_ERR_INVALID_ARG);
-            CHECK(rt_light_hits(hits.get(), &s, kDir, 2, 0, 2, 0, px.get()) == RT_ERR_INVALID_ARG);
-        }
+        const Call to_px{hits.get(), &s, kDir, 2, 0, 2, px.get()};
+        refused_formats(lit, to_px);
+        refusals([&](const Call& c) { return lit(c, 0); }, to_px, &hits[3], 2);
+        refusals(own, Call{hits.get(), &s, kDir, 2, 0, 2, surf.get()}, &hits[3], 2);
     }
-    if (failures) return 1;
-    std::printf("light args check ok\n");
-    return 0;
+    empty_scene<rt_surface>(light.get(), own, lit, is_zero_surface);
+    return finish("light");
 }

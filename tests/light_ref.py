@@ -70,6 +70,18 @@ def cached_hits(oracle, key, scene, w, h, rows=None, ray_dir=REF_DIR, x_begin=0)
     return _CACHE[k]
 
 
+def restated(ref, oracle, key, scene, w, h, rows=None, ray_dir=REF_DIR):
+    """(cached_hits, ref(oracle, scene, hits, row_begin, ray_dir)), once per
+    restatement `ref`, key, direction and light set: the CPU and the GPU file
+    of one pass share it."""
+    k = (ref.__name__, key, w, h, rows, np.asarray(ray_dir, F32).tobytes(),
+         np.asarray(scene.lights, F32).tobytes())
+    if k not in _CACHE:
+        hits = cached_hits(oracle, key, scene, w, h, rows, ray_dir)
+        _CACHE[k] = (hits, ref(oracle, scene, hits, rows[0] if rows else 0, ray_dir))
+    return _CACHE[k]
+
+
 def _unit(mx, my, mz):
     length = np.sqrt((mx * mx + my * my) + mz * mz)
     return mx / length, my / length, mz / length

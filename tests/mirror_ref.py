@@ -2,7 +2,7 @@
 
 A numpy restatement of DESIGN.md §3.1e for rt_bounce_hits /
 rt_light_hits_mirrored.  The pieces are tests/reflect_ref.py's (`mirror_dir`,
-`sphere_sf`, `tri_sf`, `factor_at`) and tests/shadow_reflect_ref.py's
+`walk`, `normal_at`, `factor_at`, `ramp`, `mix`) and tests/shadow_reflect_ref.py's
 `shadow_at`; what is added here is the level loop (`chain_ref`: the geometry of
 every level, followed without regard to reflectivity) and the backward blend
 (`Chain.lit`), one ufunc per written operation (numpy never contracts), in the
@@ -90,73 +90,6 @@ WAVE_REFLECTIVITY = np.array([1, 0, 1, 0, 1, 1, 1, 1, 1], F32)
 # ---------------------------------------------------------------------------
 # The restatement
 # ---------------------------------------------------------------------------
-def _unit(mx, my, mz):
-    with np.errstate(all="ignore"):
-        length = np.sqrt((mx * mx + my * my) + mz * mz)
-        return mx / length, my / length, mz / length
-
-
-def walk(scene, own, p, R):
-    """bounce_walk from the points p along R over every object but `own` (-1:
-    no walk there): cubes 0 .. nc-1 with triangles 0 .. 11, then spheres; a
-    candidate is taken iff sf < best.  (best, obj2, tri2)."""
-    cubes = np.ascontiguousarray(scene.cube_vertices, F32).reshape(-1, 36, 4)
-    centres = np.ascontiguousarray(scene.sphere_origins, F32).reshape(-1, 4)
-    radius = np.ascontiguousarray(scene.sphere_radius, F32).reshape(-1)
-    nc = len(cubes)
-    best = np.full(own.shape, K_FAR, F32)
-    obj2 = np.full(own.shape, -1, np.int32)
-    tri2 = np.full(own.shape, -1, np.int32)
-    active = own >= 0
-    with np.errstate(all="ignore"):
-        for j in range(nc):
-            cand = active & (own != j)
-            if not cand.any():
-                continue
-            for k in range(12):
-                ok, sf = rr.tri_sf(p, R, *cubes[j, 3 * k:3 * k + 3])
-                take = cand & ok & (sf < best)
-                best, obj2, tri2 = (np.where(take, sf, best), np.where(take, j, obj2),
-                                    np.where(take, k, tri2))
-        for s in range(len(radius)):
-            cand = active & (own != nc + s)
-            if not cand.any():
-                continue
-            ok, sf, _ = rr.sphere_sf(p, R, centres[s], radius[s])
-            take = cand & ok & (sf < best)
-            best, obj2, tri2 = (np.where(take, sf, best), np.where(take, nc + s, obj2),
-                                np.where(take, -1, tri2))
-    return best.astype(F32), obj2.astype(np.int32), tri2.astype(np.int32)
-
-
-def normal_at(scene, obj2, tri2, p2, R):
-    """bounce_normal: the unit normal of (obj2, tri2) at p2, turned against R
-    (0 where obj2 is -1)."""
-    cubes = np.ascontiguousarray(scene.cube_vertices, F32).reshape(-1, 36, 4)
-    centres = np.ascontiguousarray(scene.sphere_origins, F32).reshape(-1, 4)
-    nc = len(cubes)
-    n2 = [np.zeros(obj2.shape, F32) for _ in range(3)]
-    on_cube = (obj2 >= 0) & (obj2 < nc)
-    with np.errstate(all="ignore"):
-        for j, k in sorted({(int(a), int(b)) for a, b in zip(obj2[on_cube], tri2[on_cube])}):
-            v0, v1, v2 = cubes[j, 3 * k, :3], cubes[j, 3 * k + 1, :3], cubes[j, 3 * k + 2, :3]
-            e1, e2 = v1 - v0, v2 - v0
-            u = _unit(e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
-                      e1[0] * e2[1] - e1[1] * e2[0])
-            at = (obj2 == j) & (tri2 == k)
-            for c in range(3):
-                n2[c][at] = u[c]
-        sph = obj2 >= nc
-        if sph.any():
-            c = centres[obj2[sph] - nc]
-            u = _unit(p2[0][sph] - c[:, 0], p2[1][sph] - c[:, 1], p2[2][sph] - c[:, 2])
-            for i in range(3):
-                n2[i][sph] = u[i]
-        s = (n2[0] * R[0] + n2[1] * R[1]) + n2[2] * R[2]
-        flip = s > 0
-        return [np.where(flip, -a, a) for a in n2]
-
-
 class Level:
     """One level of every pixel's chain: obj (-1: the chain did not get here),
     the point p, the faced normal n, the direction D it was reached along, the
@@ -205,11 +138,7 @@ class Chain:
         with np.errstate(all="ignore"):
             for j in range(depth + 1):
                 lv = self.levels[j]
-                normalised = (lv.T - F32(0.0)) / (F32(180.0) - F32(0.0))
-                scalar = F32(255.0) - (normalised * F32(255.0))
-                if j >= 1:
-                    scalar = np.where(scalar > 0, scalar, F32(0.0))
-                lit = scalar * self.factor(j, shadows)
+                lit = rr.ramp(lv.T, j >= 1) * self.factor(j, shadows)
                 colour = table[lv.obj]
                 a = [lit * colour[..., ch] for ch in range(3)]
                 r = rtable[lv.obj] if j < depth else np.zeros(lv.obj.shape, F32)
@@ -229,7 +158,7 @@ class Chain:
             for reached, goes, a, r in reversed(self.run(reflectivity, depth, shadows)):
                 for ch in range(3):
                     C[ch] = np.where(reached & ~goes, a[ch], C[ch])
-                    C[ch] = np.where(goes, a[ch] + r * (C[ch] - a[ch]), C[ch])
+                    C[ch] = np.where(goes, rr.mix(a[ch], C[ch], r), C[ch])
             for ch in range(3):
                 out[..., ch] = np.where(self.alive, lr.x86_int(C[ch]), out[..., ch])
         return out
@@ -272,11 +201,11 @@ def chain_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR, depth=MAX_BOUNC
     with np.errstate(all="ignore"):
         for _ in range(depth):
             R = rr.mirror_dir({"nx": lv.n[0], "ny": lv.n[1], "nz": lv.n[2]}, np.array(lv.D))
-            best, obj2, tri2 = walk(scene, lv.obj, lv.p, R)
+            best, obj2, tri2, _ = rr.walk(scene, lv.obj, lv.p, R)
             nx = Level()
             nx.obj, nx.best = obj2, best
             nx.p = (lv.p[0] + best * R[0], lv.p[1] + best * R[1], lv.p[2] + best * R[2])
-            nx.n = normal_at(scene, obj2, tri2, nx.p, R)
+            nx.n = rr.normal_at(scene, obj2, tri2, nx.p, R)
             nx.D, nx.T = list(R), lv.T + best
             c.levels.append(nx)
             lv = nx
@@ -302,3 +231,47 @@ def wave_kinds(steps, alive):
     reached1, reached2 = steps[1][0].reshape(-1, 64), steps[2][0].reshape(-1, 64)
     return (hit.any(1) & (reached1 == hit).all(1) & ~reached2.any(1),
             hit.any(1) & (reached2 == hit).all(1), alone(steps, alive))
+
+
+# ---------------------------------------------------------------------------
+# What the tests of both files (CPU and GPU) share
+# ---------------------------------------------------------------------------
+def restated(oracle, key, scene, w, h, rows=None, d=REF_DIR):
+    """(hits, chain_ref's geometry), once per key, direction and light set."""
+    return lr.restated(chain_ref, oracle, key, scene, w, h, rows, d)
+
+
+def mixed(scene):
+    """One reflectivity per slot: 1, 0.25, 1, 0, 1, 0.25, ..."""
+    return np.resize(np.array([1, 0.25, 1, 0], F32), scene.num_cubes + scene.num_spheres)
+
+
+def chain_facts(c):
+    """What the chain scene is there for."""
+    refl = CHAIN_REFLECTIVITY
+    assert set(refl.tolist()) == {0.0, 0.25, 1.0}
+    walks, last, cause = c.stats(refl, 8)
+    assert (walks == 1).sum() >= 100 and (walks == 2).sum() >= 100  # 14961, 659
+    assert (walks >= 3).sum() >= 100                                # 154
+    # ended at a level >= 2 by each cause, at depth 3: 98, 27, 56
+    _, last, cause = c.stats(refl, 3)
+    for name in ("miss", "matte", "depth"):
+        assert (cause[name] & (last >= 2)).sum() >= 20, name
+    # the primary object is a candidate again: the hovering sphere, the face, the sphere
+    went_on = c.run(refl, 8, False)[1][1]
+    back = went_on & (c.levels[2].obj == c.levels[0].obj)
+    assert back.sum() >= 20  # 58
+
+
+def corridor_facts(c):
+    """At least 64 pixels reach level RT_MAX_BOUNCES, the ramp long dead."""
+    deep = c.bounce(MAX_BOUNCES)["object"] >= 0
+    assert deep.sum() >= 64  # 1632
+    assert (c.levels[MAX_BOUNCES].T[deep] > 180).all()
+    assert (c.levels[2].T[c.levels[2].obj >= 0] > 180).sum() >= 64  # the clamp, early on
+
+
+def wave_facts(c):
+    steps = c.run(WAVE_REFLECTIVITY, 8, False)
+    for kind in wave_kinds(steps, c.alive):  # 44, 41, 78
+        assert kind.sum() >= 20

@@ -1,6 +1,6 @@
 // reflect_args_check.cpp -- rt_reflect_hits / rt_light_hits_reflected
-// (csrc/rt_light.cpp with csrc/rt_args.cpp) as a stand-alone program like
-// shadow_args_check.cpp: tests/test_reflect_hits.py builds it with
+// (csrc/rt_light.cpp with csrc/rt_args.cpp) as a stand-alone program on
+// tests/light_check.h: tests/test_reflect_hits.py builds it with
 // -fsanitize=address,undefined and runs it.  No GPU.
 //
 //   - exactly-sized heap arrays for the frame, the scene and every output
@@ -12,113 +12,58 @@
 //   - reflectivity 0, 0.25 and 1, and the refused ones;
 //   - the argument checks.
 // Exit 0 and "reflect args check ok" on success.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <memory>
+#include "light_check.h"
 
-#include "rt_hip.h"
-
-namespace {
-
-int failures = 0;
-
-#define CHECK(cond)                                                              \
-    do {                                                                         \
-        if (!(cond)) {                                                           \
-            std::fprintf(stderr, "%s:%d: check failed: %s\n", __FILE__, __LINE__, \
-                         #cond);                                                 \
-            ++failures;                                                          \
-        }                                                                        \
-    } while (0)
-
-const float kDir[4] = {0.0f, 0.0f, -1.0f, -1.0f};
-const int32_t kBlack[4] = {0, 0, 0, 255};
-
-// an axis-aligned box as a cube's float4[36], Cube.cpp's corner order
-void box(float* verts, const float lo[3], const float hi[3]) {
-    // corner bit0 = x, bit1 = y, bit2 = z (set = hi)
-    const unsigned char corners[36] = {0, 4, 6, 3, 0, 2, 5, 0, 1, 3, 1, 0, 0, 6, 2, 5, 4, 0,
-                                       6, 4, 5, 7, 1, 3, 1, 7, 5, 7, 3, 2, 7, 2, 6, 7, 6, 5};
-    for (int k = 0; k < 36; ++k) {
-        for (int a = 0; a < 3; ++a) verts[4 * k + a] = (corners[k] >> a & 1u) ? hi[a] : lo[a];
-        verts[4 * k + 3] = 1.0f;
-    }
-}
-
-bool is_miss(const rt_hit& h) { return h.t == 300000.0f && h.object == -1; }
-
-}  // namespace
+using namespace light_check;
 
 int main() {
-    // ---- cube 0 (the face z = -50), cube 1 (the box), sphere 0 (slot 2),
-    // sphere 1 (slot 3, in front of the ray origins), one light ----------------
-    std::unique_ptr<float[]> verts(new float[2 * 144]);
+    KindsScene kinds;
+    const rt_scene& s = kinds.s;
+    auto own = [](const Call& c) {
+        return rt_reflect_hits(c.hits, c.scene, c.dir, c.w, c.rb, c.re, (rt_hit*)c.out);
+    };
+    auto lit_at = [](float r) {
+        return [r](const Call& c, int32_t fmt) {
+            return rt_light_hits_reflected(c.hits, c.scene, c.dir, c.w, c.rb, c.re, r, fmt, c.out);
+        };
+    };
     {
-        const float lo0[3] = {-6.0f, -6.0f, -70.0f}, hi0[3] = {134.0f, 134.0f, -50.0f};
-        const float lo1[3] = {85.0f, 58.0f, -15.0f}, hi1[3] = {97.0f, 70.0f, -3.0f};
-        box(verts.get(), lo0, hi0);
-        box(verts.get() + 144, lo1, hi1);
-    }
-    std::unique_ptr<float[]> cube_col(new float[8]{1.0f, 0.7f, 0.3f, 255.0f, 0.3f, 0.5f, 1.0f, 255.0f});
-    std::unique_ptr<float[]> sph_org(new float[8]{64.0f, 64.0f, -30.0f, 1.0f, 118.0f, 64.0f, 12.0f, 1.0f});
-    std::unique_ptr<float[]> sph_rad(new float[2]{12.0f, 4.0f});
-    std::unique_ptr<float[]> sph_col(new float[8]{0.2f, 0.9f, 0.4f, 255.0f, 0.9f, 0.9f, 0.1f, 255.0f});
-    std::unique_ptr<float[]> light(new float[4]{154.0f, 64.0f, 40.0f, 1.0f});
-    rt_scene s{};
-    s.num_cubes = 2;
-    s.cube_vertices = verts.get();
-    s.cube_colours = cube_col.get();
-    s.num_spheres = 2;
-    s.sphere_origins = sph_org.get();
-    s.sphere_radius = sph_rad.get();
-    s.sphere_colours = sph_col.get();
-    s.num_lights = 1;
-    s.lights = light.get();
-
-    // rows 60..67 of the 128-wide frame, every pixel on the face (t = 50) but
-    // (64, 64), the pole of sphere 0 (t = 18), (75, 64) on its flank and a miss
-    {
-        const int w = 128, rb = 60, re = 68, n = w * (re - rb);
-        std::unique_ptr<rt_hit[]> hits(new rt_hit[n]);
-        for (int i = 0; i < n; ++i) hits[i] = rt_hit{50.0f, 0};
-        hits[4 * w + 64] = rt_hit{18.0f, 2};
-        hits[4 * w + 75] = rt_hit{30.0f - std::sqrt(23.0f), 2};
-        hits[7 * w + 127] = rt_hit{300000.0f, -1};
+        Band band(true);
+        const int w = Band::w, rb = Band::rb, re = Band::re, n = Band::n;
+        rt_hit* hits = band.hits.get();
         std::unique_ptr<rt_hit[]> bounce(new rt_hit[n]);
         std::unique_ptr<int32_t[]> px(new int32_t[4 * n]);
         std::unique_ptr<int32_t[]> full(new int32_t[4 * n]);
         std::unique_ptr<int32_t[]> plain(new int32_t[4 * n]);
         std::unique_ptr<int32_t[]> zero(new int32_t[4 * n]);
         std::unique_ptr<uint32_t[]> words(new uint32_t[n]);
-        CHECK(rt_reflect_hits(hits.get(), &s, kDir, w, rb, re, bounce.get()) == RT_OK);
-        CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, 0.25f, RT_FORMAT_I32X4,
+        CHECK(rt_reflect_hits(hits, &s, kDir, w, rb, re, bounce.get()) == RT_OK);
+        CHECK(rt_light_hits_reflected(hits, &s, kDir, w, rb, re, 0.25f, RT_FORMAT_I32X4,
                                       px.get()) == RT_OK);
-        CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, 1.0f, RT_FORMAT_I32X4,
+        CHECK(rt_light_hits_reflected(hits, &s, kDir, w, rb, re, 1.0f, RT_FORMAT_I32X4,
                                       full.get()) == RT_OK);
-        CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, 0.0f, RT_FORMAT_I32X4,
+        CHECK(rt_light_hits_reflected(hits, &s, kDir, w, rb, re, 0.0f, RT_FORMAT_I32X4,
                                       zero.get()) == RT_OK);
-        CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, 0.25f, RT_FORMAT_RGBA8,
+        CHECK(rt_light_hits_reflected(hits, &s, kDir, w, rb, re, 0.25f, RT_FORMAT_RGBA8,
                                       words.get()) == RT_OK);
-        CHECK(rt_light_hits(hits.get(), &s, kDir, w, rb, re, RT_FORMAT_I32X4, plain.get()) == RT_OK);
+        CHECK(rt_light_hits(hits, &s, kDir, w, rb, re, RT_FORMAT_I32X4, plain.get()) == RT_OK);
         // reflectivity 0: rt_light_hits' frame
         CHECK(std::memcmp(zero.get(), plain.get(), sizeof(int32_t) * 4 * n) == 0);
         // (118, 64): straight back from z = -50 to the lowest point of sphere 1, z = 8
-        CHECK(bounce[4 * w + 118].object == 3 && bounce[4 * w + 118].t == 58.0f);
-        CHECK(std::memcmp(&px[4 * (4 * w + 118)], &plain[4 * (4 * w + 118)], 16) != 0);
+        CHECK(bounce[Band::kUnder].object == 3 && bounce[Band::kUnder].t == 58.0f);
+        CHECK(std::memcmp(&px[4 * Band::kUnder], &plain[4 * Band::kUnder], 16) != 0);
         // (5, 60) mirrors nothing: a + r * (0 - a)
-        CHECK(is_miss(bounce[5]) && plain[4 * 5] > 0);
-        CHECK(px[4 * 5] > 0 && px[4 * 5] < plain[4 * 5]);
-        CHECK(std::memcmp(&full[4 * 5], kBlack, sizeof kBlack) == 0);
+        CHECK(is_miss(bounce[Band::kSees]) && plain[4 * Band::kSees] > 0);
+        CHECK(px[4 * Band::kSees] > 0 && px[4 * Band::kSees] < plain[4 * Band::kSees]);
+        CHECK(is_black(&full[4 * Band::kSees]));
         // the pole of sphere 0 mirrors straight back, past everything
-        CHECK(is_miss(bounce[4 * w + 64]));
+        CHECK(is_miss(bounce[Band::kPole]));
         // its flank mirrors down onto the face
-        CHECK(bounce[4 * w + 75].object == 0 && bounce[4 * w + 75].t > 20.0f &&
-              bounce[4 * w + 75].t < 100.0f);
+        CHECK(bounce[Band::kFlank].object == 0 && bounce[Band::kFlank].t > 20.0f &&
+              bounce[Band::kFlank].t < 100.0f);
         // the miss
         CHECK(is_miss(bounce[n - 1]) && words[n - 1] == 0xFF000000u);
-        CHECK(std::memcmp(&px[4 * (n - 1)], kBlack, sizeof kBlack) == 0);
+        CHECK(is_black(&px[4 * (n - 1)]));
         for (int i = 0; i < n; ++i) {
             CHECK(bounce[i].object >= -1 && bounce[i].object < 4);
             CHECK(hits[i].object < 0 || bounce[i].object != hits[i].object);
@@ -126,74 +71,16 @@ int main() {
         }
 
         // ---- arguments ----------------------------------------------------------
-        CHECK(rt_reflect_hits(nullptr, &s, kDir, w, rb, re, bounce.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_reflect_hits(hits.get(), nullptr, kDir, w, rb, re, bounce.get()) ==
-              RT_ERR_INVALID_ARG);
-        CHECK(rt_reflect_hits(hits.get(), &s, nullptr, w, rb, re, bounce.get()) ==
-              RT_ERR_INVALID_ARG);
-        CHECK(rt_reflect_hits(hits.get(), &s, kDir, w, rb, re, nullptr) == RT_ERR_INVALID_ARG);
-        CHECK(rt_reflect_hits(hits.get(), &s, kDir, 0, rb, re, bounce.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_reflect_hits(hits.get(), &s, kDir, w, -1, re, bounce.get()) == RT_ERR_INVALID_ARG);
-        CHECK(rt_reflect_hits(hits.get(), &s, kDir, w, re, re, bounce.get()) == RT_ERR_INVALID_ARG);
-        for (float r : {0.0f, 0.5f}) {
-            CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, r, 0, nullptr) ==
-                  RT_ERR_INVALID_ARG);
-            CHECK(rt_light_hits_reflected(nullptr, &s, kDir, w, rb, re, r, 0, px.get()) ==
-                  RT_ERR_INVALID_ARG);
-            for (int32_t fmt : {2, (int32_t)RT_FORMAT_HIT, 4, -1})
-                CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, r, fmt, px.get()) ==
-                      RT_ERR_INVALID_ARG);
-        }
-        for (float r : {-0.1f, 1.5f, NAN, INFINITY, -INFINITY, std::nextafter(1.0f, 2.0f)})
-            for (int32_t fmt : {(int32_t)RT_FORMAT_I32X4, (int32_t)RT_FORMAT_RGBA8})
-                CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, r, fmt, px.get()) ==
-                      RT_ERR_INVALID_ARG);
-        rt_scene bad = s;
-        bad.lights = nullptr;
-        CHECK(rt_reflect_hits(hits.get(), &bad, kDir, w, rb, re, bounce.get()) ==
-              RT_ERR_INVALID_ARG);
-        bad = s;
-        bad.num_lights = -1;
-        CHECK(rt_light_hits_reflected(hits.get(), &bad, kDir, w, rb, re, 0.5f, 0, px.get()) ==
-              RT_ERR_INVALID_ARG);
-        for (int32_t obj : {4, -2, INT32_MAX, INT32_MIN}) {
-            hits[n - 1].object = obj;
-            CHECK(rt_reflect_hits(hits.get(), &s, kDir, w, rb, re, bounce.get()) ==
-                  RT_ERR_INVALID_ARG);
-            for (float r : {0.0f, 0.5f})
-                CHECK(rt_light_hits_reflected(hits.get(), &s, kDir, w, rb, re, r, 0, px.get()) ==
-                      RT_ERR_INVALID_ARG);
-        }
+        refusals(own, Call{hits, &s, kDir, w, rb, re, bounce.get()}, &hits[n - 1],
+                 KindsScene::slots);
+        reflectivity_refusals(lit_at, Call{hits, &s, kDir, w, rb, re, px.get()}, &hits[n - 1],
+                              KindsScene::slots);
     }
-
-    // ---- an empty scene with NULL arrays: every pixel a miss -----------------
-    {
-        rt_scene empty{};
-        const int w = 5, rows = 3;
-        std::unique_ptr<rt_hit[]> hits(new rt_hit[w * rows]);
-        for (int i = 0; i < w * rows; ++i) hits[i] = rt_hit{300000.0f, -1};
-        std::unique_ptr<rt_hit[]> bounce(new rt_hit[w * rows]);
-        std::unique_ptr<int32_t[]> px(new int32_t[4 * w * rows]);
-        std::unique_ptr<uint32_t[]> words(new uint32_t[w * rows]);
-        for (int with_light = 0; with_light < 2; ++with_light) {
-            empty.lights = with_light ? light.get() : nullptr;
-            empty.num_lights = with_light;
-            CHECK(rt_reflect_hits(hits.get(), &empty, kDir, w, 0, rows, bounce.get()) == RT_OK);
-            CHECK(rt_light_hits_reflected(hits.get(), &empty, kDir, w, 0, rows, 1.0f,
-                                          RT_FORMAT_I32X4, px.get()) == RT_OK);
-            CHECK(rt_light_hits_reflected(hits.get(), &empty, kDir, w, 0, rows, 0.0f,
-                                          RT_FORMAT_RGBA8, words.get()) == RT_OK);
-            for (int i = 0; i < w * rows; ++i) {
-                CHECK(is_miss(bounce[i]) && words[i] == 0xFF000000u);
-                CHECK(std::memcmp(&px[4 * i], kBlack, sizeof kBlack) == 0);
-            }
-        }
-        // any object is out of range in an empty scene
-        hits[w * rows - 1].object = 0;
-        CHECK(rt_reflect_hits(hits.get(), &empty, kDir, w, 0, rows, bounce.get()) ==
-              RT_ERR_INVALID_ARG);
-    }
-    if (failures) return 1;
-    std::printf("reflect args check ok\n");
-    return 0;
+    empty_scene<rt_hit>(
+        kinds.light.get(), own,
+        [&](const Call& c, int32_t fmt) {
+            return lit_at(fmt == RT_FORMAT_RGBA8 ? 0.0f : 1.0f)(c, fmt);
+        },
+        [](const rt_hit& h) { return is_miss(h); });
+    return finish("reflect");
 }

@@ -199,6 +199,100 @@ def _unit(mx, my, mz):
         return mx / length, my / length, mz / length
 
 
+def walk(scene, own, p, R):
+    """bounce_walk from the points p along R over every object but `own` (-1:
+    no walk there): cubes 0 .. nc-1 with triangles 0 .. 11, then spheres; a
+    candidate is taken iff sf < best.  (best, obj2, tri2, far_root: the
+    winning sphere root was s1)."""
+    cubes = np.ascontiguousarray(scene.cube_vertices, F32).reshape(-1, 36, 4)
+    centres = np.ascontiguousarray(scene.sphere_origins, F32).reshape(-1, 4)
+    radius = np.ascontiguousarray(scene.sphere_radius, F32).reshape(-1)
+    nc = len(cubes)
+    best = np.full(own.shape, K_FAR, F32)
+    obj2 = np.full(own.shape, -1, np.int32)
+    tri2 = np.full(own.shape, -1, np.int32)
+    far_root = np.zeros(own.shape, bool)
+    active = own >= 0
+    with np.errstate(all="ignore"):
+        for j in range(nc):
+            cand = active & (own != j)
+            if not cand.any():
+                continue
+            for k in range(12):
+                ok, sf = tri_sf(p, R, *cubes[j, 3 * k:3 * k + 3])
+                take = cand & ok & (sf < best)
+                best, obj2, tri2 = (np.where(take, sf, best), np.where(take, j, obj2),
+                                    np.where(take, k, tri2))
+        for s in range(len(radius)):
+            cand = active & (own != nc + s)
+            if not cand.any():
+                continue
+            ok, sf, far = sphere_sf(p, R, centres[s], radius[s])
+            take = cand & ok & (sf < best)
+            best, obj2, tri2 = (np.where(take, sf, best), np.where(take, nc + s, obj2),
+                                np.where(take, -1, tri2))
+            far_root = np.where(take, far, far_root)
+    return best.astype(F32), obj2.astype(np.int32), tri2.astype(np.int32), far_root
+
+
+def normal_at(scene, obj2, tri2, p2, R):
+    """bounce_normal: the unit normal of (obj2, tri2) at p2, turned against R
+    (0 where obj2 is -1)."""
+    cubes = np.ascontiguousarray(scene.cube_vertices, F32).reshape(-1, 36, 4)
+    centres = np.ascontiguousarray(scene.sphere_origins, F32).reshape(-1, 4)
+    nc = len(cubes)
+    n2 = [np.zeros(obj2.shape, F32) for _ in range(3)]
+    on_cube = (obj2 >= 0) & (obj2 < nc)
+    with np.errstate(all="ignore"):
+        for j, k in sorted({(int(a), int(b)) for a, b in zip(obj2[on_cube], tri2[on_cube])}):
+            v0, v1, v2 = cubes[j, 3 * k, :3], cubes[j, 3 * k + 1, :3], cubes[j, 3 * k + 2, :3]
+            e1, e2 = v1 - v0, v2 - v0
+            u = _unit(e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
+                      e1[0] * e2[1] - e1[1] * e2[0])
+            at = (obj2 == j) & (tri2 == k)
+            for c in range(3):
+                n2[c][at] = u[c]
+        sph = obj2 >= nc
+        if sph.any():
+            c = centres[obj2[sph] - nc]
+            u = _unit(p2[0][sph] - c[:, 0], p2[1][sph] - c[:, 1], p2[2][sph] - c[:, 2])
+            for i in range(3):
+                n2[i][sph] = u[i]
+        s = (n2[0] * R[0] + n2[1] * R[1]) + n2[2] * R[2]
+        flip = s > 0
+        return [np.where(flip, -a, a) for a in n2]
+
+
+def ramp(T, clamped):
+    """The depth ramp at depth T; `clamped`: never below 0 (every level but
+    the pixel's own: past the ramp's end a bounce adds no negative light)."""
+    with np.errstate(all="ignore"):
+        normalised = (T - F32(0.0)) / (F32(180.0) - F32(0.0))
+        scalar = F32(255.0) - (normalised * F32(255.0))
+        return np.where(scalar > 0, scalar, F32(0.0)) if clamped else scalar
+
+
+def mix(a, b, r):
+    """a + r * (b - a), in float32."""
+    with np.errstate(all="ignore"):
+        return a + r * (b - a)
+
+
+def blended(lit, r, lit1, lit2, rf):
+    """`lit` with (int)(a + r * (b - a)) in the colour channels where `rf`
+    (a Reflected) blends: a = lit1 * the pixel's colour, b = lit2 * the
+    bounce's."""
+    r = F32(r)
+    if r == 0:
+        return lit
+    out = np.array(lit)
+    with np.errstate(all="ignore"):
+        for ch in range(3):
+            a, b = lit1 * rf._colour[..., ch], lit2 * rf._colour2[..., ch]
+            out[..., ch] = np.where(rf._blend, lr.x86_int(mix(a, b, r)), out[..., ch])
+    return out
+
+
 class Reflected:
     """bounce: the HIT_DTYPE frame of rt_reflect_hits.  tri2: the bounce's
     triangle (-1: sphere or miss).  kinds: {(receiver, target): bool frame}
@@ -209,61 +303,24 @@ class Reflected:
     (NaN where the bounce missed)."""
 
     def mirrored(self, r):
-        r = F32(r)
-        if r == 0:
-            return self.lit
-        out = np.array(self.lit)
-        with np.errstate(all="ignore"):
-            for ch in range(3):
-                a = self._lit * self._colour[..., ch]
-                b = self._lit2 * self._colour2[..., ch]
-                out[..., ch] = np.where(self._blend, lr.x86_int(a + r * (b - a)), out[..., ch])
-        return out
+        return blended(self.lit, r, self._lit, self._lit2, self)
 
 
 def reflect_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR):
+    """Level 0, one walk, the normal and the factor at the bounce point."""
     n, w = hits.shape
     t, obj = hits["t"], hits["object"]
     nc = scene.num_cubes
     lights = np.ascontiguousarray(scene.lights, F32).reshape(-1, 4)
-    cubes = np.ascontiguousarray(scene.cube_vertices, F32).reshape(-1, 36, 4)
-    centres = np.ascontiguousarray(scene.sphere_origins, F32).reshape(-1, 4)
-    radius = np.ascontiguousarray(scene.sphere_radius, F32).reshape(-1)
     r = Reflected()
     r.surf = lr.surfaces_ref(oracle, scene, hits, row_begin, ray_dir)
     r.k = lr.light_factor_ref(scene, hits, r.surf, row_begin, ray_dir)
     r.lit = lr.lit_ref(oracle, scene, hits, row_begin, ray_dir, surf=r.surf, k=r.k)
     r.p = p = lr.hit_points(hits, row_begin, ray_dir)
     r.R = R = mirror_dir(r.surf, ray_dir)
-
-    # the closest-hit walk: cubes 0..nc-1 with triangles 0..11, then spheres
-    best = np.full((n, w), K_FAR, F32)
-    obj2 = np.full((n, w), -1, np.int32)
-    tri2 = np.full((n, w), -1, np.int32)
-    r.far_root = np.zeros((n, w), bool)
-    active = obj >= 0
-    with np.errstate(all="ignore"):
-        for j in range(nc):
-            cand = active & (obj != j)
-            if not cand.any():
-                continue
-            for k in range(12):
-                ok, sf = tri_sf(p, R, *cubes[j, 3 * k:3 * k + 3])
-                take = cand & ok & (sf < best)
-                best, obj2, tri2 = (np.where(take, sf, best), np.where(take, j, obj2),
-                                    np.where(take, k, tri2))
-        for s in range(len(radius)):
-            cand = active & (obj != nc + s)
-            if not cand.any():
-                continue
-            ok, sf, far = sphere_sf(p, R, centres[s], radius[s])
-            take = cand & ok & (sf < best)
-            best, obj2, tri2 = (np.where(take, sf, best), np.where(take, nc + s, obj2),
-                                np.where(take, -1, tri2))
-            r.far_root = np.where(take, far, r.far_root)
+    best, obj2, r.tri2, r.far_root = walk(scene, obj.astype(np.int32), p, R)
     r.bounce = np.empty((n, w), hit_dtype())
     r.bounce["t"], r.bounce["object"] = best, obj2
-    r.tri2 = tri2.astype(np.int32)
     hit2 = obj2 >= 0
     kind = {"cube": (obj >= 0) & (obj < nc), "sphere": obj >= nc}
     kind2 = {"cube": hit2 & (obj2 < nc), "sphere": obj2 >= nc}
@@ -274,38 +331,72 @@ def reflect_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR):
                             np.ascontiguousarray(scene.sphere_colours, F32).reshape(-1, 4),
                             np.array([[0, 0, 0, 255]], F32)])  # [-1]: nothing
     r._colour, r._colour2 = table[obj], table[obj2]
-    r._blend = active & ~(t == K_FAR)
+    r._blend = (obj >= 0) & ~(t == K_FAR)
     with np.errstate(all="ignore"):
-        normalised = (t - F32(0.0)) / (F32(180.0) - F32(0.0))
-        scalar = F32(255.0) - (normalised * F32(255.0))
-        r._lit = scalar * r.k
+        r._lit = ramp(t, False) * r.k
         p2 = (p[0] + best * R[0], p[1] + best * R[1], p[2] + best * R[2])
-        n2 = [np.zeros((n, w), F32) for _ in range(3)]
-        for j, k in sorted({(int(a), int(b)) for a, b in zip(obj2[kind2["cube"]],
-                                                              tri2[kind2["cube"]])}):
-            v0, v1, v2 = cubes[j, 3 * k, :3], cubes[j, 3 * k + 1, :3], cubes[j, 3 * k + 2, :3]
-            e1, e2 = v1 - v0, v2 - v0
-            u = _unit(e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
-                      e1[0] * e2[1] - e1[1] * e2[0])
-            at = (obj2 == j) & (tri2 == k)
-            for c in range(3):
-                n2[c][at] = u[c]
-        sph = kind2["sphere"]
-        if sph.any():
-            c = centres[obj2[sph] - nc]
-            u = _unit(p2[0][sph] - c[:, 0], p2[1][sph] - c[:, 1], p2[2][sph] - c[:, 2])
-            for i in range(3):
-                n2[i][sph] = u[i]
-        s = (n2[0] * R[0] + n2[1] * R[1]) + n2[2] * R[2]
-        flip = s > 0
-        n2 = [np.where(flip, -a, a) for a in n2]
-        k2 = factor_at(n2, p2, lights) if len(lights) else np.ones((n, w), F32)
-        t2 = t + best
-        normalised2 = (t2 - F32(0.0)) / (F32(180.0) - F32(0.0))
-        scalar2 = F32(255.0) - (normalised2 * F32(255.0))
-        r.scalar2 = np.where(hit2, scalar2, F32(np.nan))
-        scalar2 = np.where(scalar2 > 0, scalar2, F32(0.0))
-        r._lit2 = np.where(hit2, scalar2 * k2, F32(0.0)).astype(F32)
+        r.n2 = normal_at(scene, obj2, r.tri2, p2, R)
+        k2 = factor_at(r.n2, p2, lights) if len(lights) else np.ones((n, w), F32)
+        r.scalar2 = np.where(hit2, ramp(t + best, False), F32(np.nan))
+        r._lit2 = np.where(hit2, ramp(t + best, True) * k2, F32(0.0)).astype(F32)
     r.k2 = np.where(hit2, k2, F32(np.nan))
-    r.n2 = n2
     return r
+
+
+# ---------------------------------------------------------------------------
+# What the tests of both files (CPU and GPU) share
+# ---------------------------------------------------------------------------
+def restated(oracle, key, scene, w, h, rows=None, d=REF_DIR):
+    """(hits, reflect_ref's restatement), once per key, direction and light set."""
+    return lr.restated(reflect_ref, oracle, key, scene, w, h, rows, d)
+
+
+def lone_pixel_scene(pkg):
+    """The base scene with sphere 0 moved onto pixel (0, 0), nearer than
+    everything else, and sphere 1 straight above it, in front of the ray
+    origins: the pixel mirrors it."""
+    scene = lr.with_lights(lr.base(pkg), lr.ONE_LIGHT)
+    scene.sphere_origins[0] = (0, 0, -5, 1)
+    scene.sphere_radius[0] = 3
+    scene.sphere_origins[1] = (0, 0, 20, 1)
+    scene.sphere_radius[1] = 5
+    return scene
+
+
+def check_edge(name, scene, hits, r):
+    """The restatement holds what the case of edge_cases is there for."""
+    obj, o2, k2 = hits["object"], r.bounce["object"], r.k2
+    met = o2 >= 0
+    if name in sr.EDGE_LIGHTS:
+        assert met.sum() >= 1000 and not np.isnan(k2[met]).any()
+    if name == "light_on_a_hit_point":
+        assert (k2[met] == 0).sum() >= 20 and (k2[met] == 1).sum() >= 100
+    elif name == "light_at_1e20":
+        # at 1e20 ll is infinite and c = 0; the light at 1e19 alone gives 0 < k2 < 1
+        assert ((k2 > 0) & (k2 < 1)).sum() >= 500 and not (k2[met] == 1).any()
+    elif name == "light_at_inf":
+        assert (k2[met] == 0).all()  # every c is 0 or NaN: nothing is added
+    elif name == "light_at_nan":
+        assert ((k2 > 0) & (k2 < 1)).sum() >= 500  # the finite light alone
+    elif name == "light_at_denormals":
+        assert (k2[met] == 1).sum() >= 100 and ((k2 > 0) & (k2 < 1)).sum() >= 100
+    elif name in ("light_inside_a_sphere", "light_on_a_triangle"):
+        assert (k2[met] == 0).sum() >= 50 and ((k2 > 0) & (k2 < 1)).sum() >= 500
+    elif name in ("dir_oblique", "dir_oblique_base"):
+        assert min(v.sum() for v in r.kinds.values()) >= 10
+        assert (r.R[0][met] != 0).all()
+    elif name == "dir_scaled_-1e-4":
+        # |R| = 1e-4: parameters of thousands, far roots and a ramp long past its end
+        assert met.sum() >= 500 and (r.bounce["t"][met] > 1000).sum() >= 500
+        assert r.far_root.sum() >= 100 and (r.scalar2[met] < 0).sum() >= 500
+    elif name in ("dir_scaled_-1e30", "nan_normal"):
+        on = obj >= 0
+        assert on.sum() >= 64 and np.isnan(r.surf["nx"][on]).all()
+        assert all(np.isnan(c[on]).all() for c in r.R)
+        assert scene.num_cubes + scene.num_spheres >= 2 and not met.any()
+    elif name == "minus_inf":
+        assert np.isneginf(hits["t"]).sum() > 50 and not met.any()
+    elif name == "nan_colour":
+        assert np.isnan(scene.sphere_colours).any() and (r.mirrored(1.0) == lr.INT_MIN).any()
+    elif name not in sr.EDGE_LIGHTS:
+        raise AssertionError(name)

@@ -54,6 +54,17 @@ def intersecting_spheres(pkg, lights):
                      lights=np.array(lights, F32).reshape(-1, 4))
 
 
+def lone_pixel_scene(pkg):
+    """The base scene with sphere 0 moved onto pixel (0, 0), nearer than
+    everything else, and sphere 1 between its hit point and the light."""
+    scene = lr.with_lights(lr.base(pkg), lr.ONE_LIGHT)
+    scene.sphere_origins[0] = (0, 0, -5, 1)
+    scene.sphere_radius[0] = 3
+    scene.sphere_origins[1] = (24, 20, 99, 1)  # half way from (0, 0, -2) to (48, 40, 200)
+    scene.sphere_radius[1] = 5
+    return scene
+
+
 DENORMAL = float(np.float32(1e-42))
 # name: lights of kinds_scene, 128 x 128 (tests 5 of the CPU file, 7 of the GPU file)
 EDGE_LIGHTS = {

@@ -128,17 +128,7 @@ class Combined:
     mirrored(r): rt_light_hits_shadowed_reflected's."""
 
     def mirrored(self, r):
-        r = F32(r)
-        if r == 0:
-            return self.lit
-        out = np.array(self.lit)
-        rf = self.refl
-        with np.errstate(all="ignore"):
-            for ch in range(3):
-                a = self._lit * rf._colour[..., ch]
-                b = self._lit2 * rf._colour2[..., ch]
-                out[..., ch] = np.where(rf._blend, lr.x86_int(a + r * (b - a)), out[..., ch])
-        return out
+        return rr.blended(self.lit, r, self._lit, self._lit2, self.refl)
 
 
 def shadow_reflect_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR, refl=None):
@@ -159,9 +149,61 @@ def shadow_reflect_ref(oracle, scene, hits, row_begin=0, ray_dir=REF_DIR, refl=N
     c.mask2 = np.where(c.hit2, c.at_p2.mask, np.uint32(0)).astype(np.uint32)
     c.lit = lr.lit_ref(oracle, scene, hits, row_begin, ray_dir, surf=rf.surf, k=c.k)
     with np.errstate(all="ignore"):
-        normalised = (t - F32(0.0)) / (F32(180.0) - F32(0.0))
-        scalar = F32(255.0) - (normalised * F32(255.0))
-        c._lit = scalar * c.k
-        scalar2 = np.where(rf.scalar2 > 0, rf.scalar2, F32(0.0))  # the clamp; NaN: a miss
-        c._lit2 = np.where(c.hit2, scalar2 * c.k2, F32(0.0)).astype(F32)
+        c._lit = rr.ramp(t, False) * c.k
+        c._lit2 = np.where(c.hit2, rr.ramp(t + best, True) * c.k2, F32(0.0)).astype(F32)
     return c
+
+
+# ---------------------------------------------------------------------------
+# What the tests of both files (CPU and GPU) share
+# ---------------------------------------------------------------------------
+def restated(oracle, key, scene, w, h, rows=None, d=REF_DIR):
+    """(hits, shadow_reflect_ref's restatement), once per key, direction and
+    light set, on top of reflect_ref.restated's for the same arguments."""
+    _, rf = rr.restated(oracle, key, scene, w, h, rows, d)
+
+    def shadow_reflect(oracle, scene, hits, row_begin, ray_dir):
+        return shadow_reflect_ref(oracle, scene, hits, row_begin, ray_dir, refl=rf)
+    return lr.restated(shadow_reflect, oracle, key, scene, w, h, rows, d)
+
+
+def class_facts(scene, hits, c):
+    """What the class scene is there for, each in at least one pixel (the
+    restatement's counts stand beside the bounds)."""
+    obj, obj2, nc = hits["object"], c.refl.bounce["object"], scene.num_cubes
+    a, a2 = c.at_p, c.at_p2
+    slot = np.arange(a2.by_object.shape[1])[None, :, None, None]
+    by_own = (a2.by_object & (slot == obj[None, None])).any(1)
+    by_third = (a2.by_object & (slot != obj[None, None])).any(1)
+    assert not (a2.by_object & (slot == obj2[None, None])).any()  # obj2 is left out, always
+    assert (by_third & ~by_own).any(0).sum() >= 100  # a third object alone hides the light: 365
+    assert (by_own & ~by_third).any(0).sum() >= 50   # the pixel's own object alone: 190
+    assert (a2.cast & ~a2.occluded).any(0).sum() >= 500  # an unoccluded facing light: 1268
+    assert (c.hit2 & ~a2.cast.any(0)).sum() >= 20         # no facing light: 47
+    assert a2.by_cube.any(0).sum() >= 30 and a2.by_sphere.any(0).sum() >= 100  # 78, 591
+    shadowed, shadowed2 = a.occluded.any(0), a2.occluded.any(0)
+    assert (shadowed2 & (obj2 < nc)).sum() >= 100 and (shadowed2 & (obj2 >= nc)).sum() >= 50
+    assert (shadowed & c.hit2 & ~shadowed2).sum() >= 50   # at p, not at p2: 171
+    assert (shadowed2 & ~shadowed).sum() >= 100           # at p2, not at p: 432
+    # the primary object's shadow at p2 shows in the mask and in the colour
+    own_only = (by_own & ~by_third).any(0)
+    assert (c.mask2[own_only] != 0).all()
+    assert (c.k2[own_only] < c.refl.k2[own_only]).all()
+
+
+# the first light faces nothing the bounces meet; the second, below and beside
+# the spheres, is seen from inside sphere 0 through sphere 0's own far side
+INSIDE_LIGHTS = [(32, 24, 100, 1), (100, 24, -100, 1)]
+SPECIAL_NAMES = ["twins", "sphere_tie", "ramp", "intersecting_spheres"]
+
+
+def special_scenes(pkg):
+    """name -> (scene, hit-cache key)."""
+    return {
+        "twins": (lr.with_lights(rr.twin_cubes_scene(pkg), lr.THREE_LIGHTS), "reflect_twins"),
+        "sphere_tie": (lr.with_lights(rr.sphere_tie_scene(pkg), lr.THREE_LIGHTS),
+                       "reflect_sphere_tie"),
+        "ramp": (rr.ramp_scene(pkg, lr.THREE_LIGHTS), "reflect_ramp"),
+        "intersecting_spheres": (sr.intersecting_spheres(pkg, [(32, 24, 100, 1), (32, 24, 0, 1)]),
+                                 "shadow_edge_p_inside_a_sphere"),
+    }

@@ -11,21 +11,20 @@ turns every NaN into INT32_MIN: tests/test_reflect_hits.py).
 import numpy as np
 import pytest
 
-import light_edges as le
+import light_device as ld
 import light_ref as lr
 import reflect_ref as rr
 import shadow_ref as sr
-from gpu_support import H, SCENE_ARRAYS, W, device_scene
-from hit_ref import K_FAR, REF_DIR
-from light_device import (PASSES, PATTERN, check_scene_padding, compare_all, host_result,
-                          padded_device_scene, run_device, unguard, upload_hits)
-from light_ref import ONE_LIGHT, THREE_LIGHTS, base, eq
+from gpu_support import device_scene
+from hit_ref import K_FAR
+from light_device import (PASSES, check_scene_padding, compare_all, padded_device_scene,
+                          run_device, unguard, upload_hits)
+from light_ref import ONE_LIGHT, THREE_LIGHTS, eq
 
 P = "reflect"  # this file's pass of tests/light_device.py
 OUTPUTS = PASSES[P].outputs
 
 gpu = pytest.mark.gpu
-F32 = np.float32
 
 
 # --- 1. the four receiver / target kinds ----------------------------------------------
@@ -69,39 +68,18 @@ def test_wave_level_paths(pkg, rt, oracle, lights):
 
 
 # --- 3. grid edges -------------------------------------------------------------------------
-def lone_pixel_scene(pkg):
-    """The base scene with sphere 0 moved onto pixel (0, 0), nearer than
-    everything else, and sphere 1 straight above it, in front of the ray
-    origins: the pixel mirrors it."""
-    scene = lr.with_lights(base(pkg), ONE_LIGHT)
-    scene.sphere_origins[0] = (0, 0, -5, 1)
-    scene.sphere_radius[0] = 3
-    scene.sphere_origins[1] = (0, 0, 20, 1)
-    scene.sphere_radius[1] = 5
-    return scene
-
-
 @gpu
 @pytest.mark.parametrize("w,h", [(1, 1), (257, 3), (83, 31)], ids=["1x1", "257x3", "83x31"])
 def test_partial_waves_and_workgroups(pkg, rt, oracle, w, h):
     """Pixel counts that are no multiple of 64 or 256 (1, 771, 2573)."""
     torch = pytest.importorskip("torch")
-    assert (w * h) % 64 and (w * h) % 256
-    rows = (0, h)
-    if (w, h) == (1, 1):
-        scene = lone_pixel_scene(pkg)
-        hits = lr.cached_hits(oracle, "reflect_lone_pixel", scene, w, h)
-        assert hits["object"][0, 0] == scene.num_cubes
-        assert pkg.reflect_hits(hits, scene)["object"][0, 0] == scene.num_cubes + 1
-    else:
-        # (257 x 3: rows 40..42 of a 257 x 80 frame, where the base scene's objects are)
-        rows = (40, 43) if h == 3 else (0, h)
-        scene = lr.with_lights(base(pkg), ONE_LIGHT)
-        hits = lr.cached_hits(oracle, "base", scene, w, H if h == 3 else h, rows)
-        assert (pkg.reflect_hits(hits, scene, rows=rows)["object"] >= 0).sum() > 5
-    ds, keep = device_scene(torch, scene)
-    compare_all(P, pkg, rt, torch, scene, ds, hits, w, rows, label=f"{w}x{h}")
-    del keep
+
+    def facts(scene, hits, rows):
+        o2 = pkg.reflect_hits(hits, scene, rows=rows)["object"]
+        assert o2[0, 0] == scene.num_cubes + 1 if (w, h) == (1, 1) else (o2 >= 0).sum() > 5
+    ld.partial_waves_and_workgroups(P, pkg, rt, torch, oracle, w, h,
+                                    (rr.lone_pixel_scene(pkg), "reflect_lone_pixel"), ONE_LIGHT,
+                                    facts)
 
 
 # --- 4. trace, then the mirrored light, on one stream ------------------------------------------
@@ -111,26 +89,11 @@ def test_trace_then_reflected_light_on_one_stream(pkg, rt, oracle):
     non-default stream, no host synchronisation in between: the host pipeline
     (hit_ref, then the host functions) gives the same frames."""
     torch = pytest.importorskip("torch")
-    scene = lr.with_lights(base(pkg), THREE_LIGHTS)
-    hits_ref = lr.cached_hits(oracle, "base", scene, W, H)
-    ds, keep = device_scene(torch, scene)
-    hd = torch.full((H, W, 2), PATTERN, dtype=torch.int32, device="cuda:0")
-    torch.cuda.synchronize()  # uploads and fills are done before the stream starts
-    stream = torch.cuda.Stream()
-    with torch.cuda.stream(stream):
-        rt.render_device(ds, W, H, (0, H), hd.data_ptr(), ray_dir=np.array(REF_DIR, F32),
-                         fmt="hit", stream=stream.cuda_stream)
-        bufs = {what: run_device(P, pkg, rt, torch, ds, hd, W, (0, H), what,
-                                 stream=stream.cuda_stream) for what in OUTPUTS}
-    stream.synchronize()
-    assert np.array_equal(hd.cpu().numpy().view(np.uint32), lr.words(hits_ref))
-    for what, buf in bufs.items():
-        got = unguard(torch, pkg, buf, W, (0, H), what)
-        want = host_result(P, pkg, hits_ref, scene, (0, H), what)
-        assert not eq(got, want), f"{what}: {eq(got, want)}"
-        if what == "bounce":
-            assert (got["object"] >= 0).sum() > 300
-    del keep
+
+    def facts(p, what, got):
+        assert what != "bounce" or (got["object"] >= 0).sum() > 300
+    ld.trace_then_calls_on_one_stream(pkg, rt, torch, oracle,
+                                      [(P, what, ld.Extras()) for what in OUTPUTS], facts)
 
 
 # --- 5. many candidates through the scalar loops ---------------------------------------------------
@@ -138,14 +101,11 @@ def test_trace_then_reflected_light_on_one_stream(pkg, rt, oracle):
 def test_256_occluders(pkg, rt):
     """18 cubes and 40 spheres: 256 primitives, three lights."""
     torch = pytest.importorskip("torch")
-    scene = lr.with_lights(pkg.Scene.synthetic(W, H, 40, 18, seed=11, k=0.3), THREE_LIGHTS)
-    assert 12 * scene.num_cubes + scene.num_spheres == 256
-    hits, _ = rt.render(scene, W, H, fmt="hit", ray_dir=REF_DIR)
-    ds, keep = device_scene(torch, scene)
-    got = compare_all(P, pkg, rt, torch, scene, ds, hits, W, (0, H), label="256 primitives")
-    o2 = got["bounce"]["object"]
-    assert (o2 >= 0).sum() > 50 and len(np.unique(o2)) > 5
-    del keep
+
+    def facts(scene, hits, got):
+        o2 = got["bounce"]["object"]
+        assert (o2 >= 0).sum() > 50 and len(np.unique(o2)) > 5
+    ld.many_primitives(P, pkg, rt, torch, facts)
 
 
 # --- 6. foreign frames -----------------------------------------------------------------------------
@@ -155,33 +115,12 @@ def test_foreign_frames(pkg, rt, oracle, kind):
     """Ids just outside [-1, nc + ns) (the host refuses the frame; with those
     ids as -1 it gives what the kernel gives) and foreign t, on padded scenes."""
     torch = pytest.importorskip("torch")
-    scene = lr.with_lights(base(pkg), THREE_LIGHTS)
-    valid = lr.cached_hits(oracle, "base", scene, W, H)
-    given, counts = (le.foreign_ids if kind == "ids" else le.foreign_t)(valid, scene)
-    assert len(counts) == (9 if kind == "ids" else 14) and min(counts.values()) >= 4
-    obj = given["object"]
-    outside = (obj < -1) | (obj >= scene.num_cubes + scene.num_spheres)
-    mapped = np.array(given)
-    mapped["object"][outside] = -1
-    if kind == "ids":
-        assert outside.sum() == 36
-        for what in OUTPUTS:
-            with pytest.raises(pkg.RtError) as e:
-                host_result(P, pkg, given, scene, (0, H), what)
-            assert e.value.status == pkg.RT_ERR_INVALID_ARG
-    else:
-        assert not outside.any()
-        # t == 300000 beside a real object: the bounce frame walks, the lit frame does not
-        far = (given["t"] == K_FAR) & (obj >= 0)
-        assert far.sum() >= 8
-    ds, keep = padded_device_scene(torch, scene)
-    got = compare_all(P, pkg, rt, torch, scene, ds, given, W, (0, H), label=f"foreign {kind}",
-                      host_hits=mapped)
-    o2 = got["bounce"]["object"]
-    assert (o2[outside] == -1).all() and (got["bounce"]["t"][outside] == K_FAR).all()
-    assert (o2 >= 0).sum() > 300
-    check_scene_padding(torch, scene, keep)
-    del keep
+
+    def facts(got, outside):
+        o2 = got["bounce"]["object"]
+        assert (o2[outside] == -1).all() and (got["bounce"]["t"][outside] == K_FAR).all()
+        assert (o2 >= 0).sum() > 300
+    ld.foreign_frames(P, pkg, rt, torch, oracle, kind, facts)
 
 
 # --- 7. numeric edges ------------------------------------------------------------------------------
@@ -190,10 +129,7 @@ def test_foreign_frames(pkg, rt, oracle, kind):
 def test_numeric_edges(pkg, rt, oracle, name):
     torch = pytest.importorskip("torch")
     scene, w, h, d, key = rr.edge_cases(pkg)[name]
-    hits = lr.cached_hits(oracle, key, scene, w, h, None, d)
-    ds, keep = device_scene(torch, scene)
-    compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), d=d, label=name)
-    del keep
+    ld.compare_scene(P, pkg, rt, torch, oracle, key, scene, w, h, d, label=name)
 
 
 @gpu
@@ -208,16 +144,12 @@ def test_ties_far_roots_and_the_ramps_end(pkg, rt, oracle, name):
                             "shadow_edge_p_inside_a_sphere"),
         "ramp": (rr.ramp_scene(pkg, ONE_LIGHT), "reflect_ramp"),
     }[name]
-    w, h = 64, 48
-    hits = lr.cached_hits(oracle, key, scene, w, h)
-    ds, keep = device_scene(torch, scene)
-    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label=name)
+    got = ld.compare_scene(P, pkg, rt, torch, oracle, key, scene, 64, 48, label=name)
     if name == "sphere_tie":
         y, x = rr.TIE_PIXEL
         assert got["bounce"]["object"][y, x] == 0
     if name == "twins":
         assert not (got["bounce"]["object"] == 1).any()
-    del keep
 
 
 # --- 8. nothing to mirror ---------------------------------------------------------------------------
@@ -226,16 +158,9 @@ def test_ties_far_roots_and_the_ramps_end(pkg, rt, oracle, name):
 def test_empty_scene(pkg, rt, lights):
     """NULL scene arrays, with and without lights: (300000, -1), (0, 0, 0, 255)."""
     torch = pytest.importorskip("torch")
-    scene = lr.with_lights(pkg.Scene(), lights)
-    w, h = 70, 9
-    hits = np.empty((h, w), pkg.HIT_DTYPE)
-    hits["t"], hits["object"] = K_FAR, -1
-    ds, keep = device_scene(torch, scene)
-    assert not any(ds.get(k) for k in SCENE_ARRAYS[:5]) and ds["num_lights"] == len(lights)
-    got = compare_all(P, pkg, rt, torch, scene, ds, hits, w, (0, h), label="empty")
+    got = ld.empty_scene(P, pkg, rt, torch, lights)
     assert (got["bounce"]["object"] == -1).all() and (got["bounce"]["t"] == K_FAR).all()
     assert (got["i32x4"] == (0, 0, 0, 255)).all() and (got["rgba8"] == 0xFF000000).all()
-    del keep
 
 
 # --- 9. reflectivity 0 is the light pass ---------------------------------------------------------------

@@ -13,15 +13,12 @@ The Python names: the host function of the lit form is
 `light_hits_reflected`, whose parameter list tests/test_reflect_hits.py pins;
 the device method is `light_hits_reflected_device(..., shadows=True)`.
 """
-import ctypes
-import inspect
 import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import light_contract as lc
 import light_ref as lr
 import reflect_ref as rr
 import shadow_ref as sr
@@ -29,21 +26,11 @@ import shadow_reflect_ref as srr
 from gpu_support import H, W
 from hit_ref import K_FAR, REF_DIR
 from light_ref import ONE_LIGHT, THREE_LIGHTS, base, eq
-from test_reflect_hits import check_edge
 
-REPO = Path(__file__).resolve().parents[1]
 F32 = np.float32
 REFLECTIVITIES = (0.25, 1.0)
-_REFS = {}
-
-
-def restated(oracle, key, scene, w, h, rows=None, d=REF_DIR):
-    """(hits, restatement), once per key and light set."""
-    k = (key, w, h, rows, np.asarray(d, F32).tobytes(), np.asarray(scene.lights, F32).tobytes())
-    if k not in _REFS:
-        hits = lr.cached_hits(oracle, key, scene, w, h, rows, d)
-        _REFS[k] = (hits, srr.shadow_reflect_ref(oracle, scene, hits, rows[0] if rows else 0, d))
-    return _REFS[k]
+ENTRIES = lc.ENTRIES["shadow_reflect"]
+restated = srr.restated
 
 
 def compare(pkg, oracle, scene, hits, c, rows=None, d=REF_DIR, label=""):
@@ -78,34 +65,10 @@ def test_shadow_at_reproduces_shadow_ref(pkg, oracle):
 
 
 # --- 2. the classes of pixels ------------------------------------------------------------------
-def class_facts(scene, hits, c):
-    """What the class scene is there for, each in at least one pixel (the
-    restatement's counts stand beside the bounds)."""
-    obj, obj2, nc = hits["object"], c.refl.bounce["object"], scene.num_cubes
-    a, a2 = c.at_p, c.at_p2
-    slot = np.arange(a2.by_object.shape[1])[None, :, None, None]
-    by_own = (a2.by_object & (slot == obj[None, None])).any(1)
-    by_third = (a2.by_object & (slot != obj[None, None])).any(1)
-    assert not (a2.by_object & (slot == obj2[None, None])).any()  # obj2 is left out, always
-    assert (by_third & ~by_own).any(0).sum() >= 100  # a third object alone hides the light: 365
-    assert (by_own & ~by_third).any(0).sum() >= 50   # the pixel's own object alone: 190
-    assert (a2.cast & ~a2.occluded).any(0).sum() >= 500  # an unoccluded facing light: 1268
-    assert (c.hit2 & ~a2.cast.any(0)).sum() >= 20         # no facing light: 47
-    assert a2.by_cube.any(0).sum() >= 30 and a2.by_sphere.any(0).sum() >= 100  # 78, 591
-    shadowed, shadowed2 = a.occluded.any(0), a2.occluded.any(0)
-    assert (shadowed2 & (obj2 < nc)).sum() >= 100 and (shadowed2 & (obj2 >= nc)).sum() >= 50
-    assert (shadowed & c.hit2 & ~shadowed2).sum() >= 50   # at p, not at p2: 171
-    assert (shadowed2 & ~shadowed).sum() >= 100           # at p2, not at p: 432
-    # the primary object's shadow at p2 shows in the mask and in the colour
-    own_only = (by_own & ~by_third).any(0)
-    assert (c.mask2[own_only] != 0).all()
-    assert (c.k2[own_only] < c.refl.k2[own_only]).all()
-
-
 def test_the_classes(pkg, oracle):
     scene = srr.class_scene(pkg)
     hits, c = restated(oracle, "shadow_reflect_class", scene, srr.CLASS_W, srr.CLASS_H)
-    class_facts(scene, hits, c)
+    srr.class_facts(scene, hits, c)
     compare(pkg, oracle, scene, hits, c, label="classes")
     for refl, least in ((0.25, 1000), (1.0, 100)):  # the restatement: 7943 and 538 pixels
         got = pkg.light_hits_shadowed_reflected(hits, scene, refl)
@@ -185,21 +148,16 @@ def test_the_mask_is_zero_where_the_bounce_misses(pkg, oracle, name):
 
 
 # --- 4. the special scenes ------------------------------------------------------------------------
-# the first light faces nothing the bounces meet; the second, below and beside
-# the spheres, is seen from inside sphere 0 through sphere 0's own far side
-INSIDE_LIGHTS = [(32, 24, 100, 1), (100, 24, -100, 1)]
-
-
 def test_inside_a_sphere_pins_the_exclusion_rule(pkg, oracle):
     """The bounce leaves sphere 1's front inside sphere 0 and meets sphere 0
     from within (the far root): n2 is turned inward, the second light faces
     p2, and the segment to it leaves sphere 0 through its far side.  The rule
     leaves obj2 = sphere 0 out, so the light counts: k2 > 0, the mask bit clear."""
-    scene = sr.intersecting_spheres(pkg, INSIDE_LIGHTS)
+    scene = sr.intersecting_spheres(pkg, srr.INSIDE_LIGHTS)
     hits, c = restated(oracle, "shadow_edge_p_inside_a_sphere", scene, 64, 48)
     from_within = c.refl.far_root & (c.refl.bounce["object"] == 0) & (hits["object"] == 1)
     assert from_within.sum() > 100  # the restatement: 193
-    L = tuple(F32(v) - a for v, a in zip(INSIDE_LIGHTS[1][:3], c.p2))
+    L = tuple(F32(v) - a for v, a in zip(srr.INSIDE_LIGHTS[1][:3], c.p2))
     with np.errstate(all="ignore"):
         through_own = sr.sphere_occludes(c.p2, L, scene.sphere_origins[0], scene.sphere_radius[0])
     pinned = from_within & c.at_p2.cast[1] & through_own
@@ -213,24 +171,10 @@ def test_inside_a_sphere_pins_the_exclusion_rule(pkg, oracle):
     assert not (pkg.shadow_hits_reflected(hits, scene)[pinned] & 2).any()
 
 
-def special_scenes(pkg):
-    return {
-        "twins": (lr.with_lights(rr.twin_cubes_scene(pkg), THREE_LIGHTS), "reflect_twins"),
-        "sphere_tie": (lr.with_lights(rr.sphere_tie_scene(pkg), THREE_LIGHTS),
-                       "reflect_sphere_tie"),
-        "ramp": (rr.ramp_scene(pkg, THREE_LIGHTS), "reflect_ramp"),
-        "intersecting_spheres": (sr.intersecting_spheres(pkg, [(32, 24, 100, 1), (32, 24, 0, 1)]),
-                                 "shadow_edge_p_inside_a_sphere"),
-    }
-
-
-SPECIAL_NAMES = ["twins", "sphere_tie", "ramp", "intersecting_spheres"]
-
-
-@pytest.mark.parametrize("name", SPECIAL_NAMES)
+@pytest.mark.parametrize("name", srr.SPECIAL_NAMES)
 def test_special_scenes(pkg, oracle, name):
-    scenes = special_scenes(pkg)
-    assert sorted(scenes) == sorted(SPECIAL_NAMES)
+    scenes = srr.special_scenes(pkg)
+    assert sorted(scenes) == sorted(srr.SPECIAL_NAMES)
     scene, key = scenes[name]
     hits, c = restated(oracle, key, scene, 64, 48)
     o2 = c.refl.bounce["object"]
@@ -261,13 +205,13 @@ def test_base_scene(pkg, oracle, lights):
 # --- 5. numeric edges ------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", rr.EDGE_NAMES)
 def test_numeric_edges(pkg, oracle, name):
-    """Every case of reflect_ref.edge_cases; tests/test_reflect_hits.py's
+    """Every case of reflect_ref.edge_cases; tests/reflect_ref.py's
     check_edge says what each holds."""
     cases = rr.edge_cases(pkg)
     assert sorted(cases) == sorted(rr.EDGE_NAMES)
     scene, w, h, d, key = cases[name]
     hits, c = restated(oracle, key, scene, w, h, None, d)
-    check_edge(name, scene, hits, c.refl)
+    rr.check_edge(name, scene, hits, c.refl)
     if name in ("light_on_a_hit_point", "light_at_nan", "light_at_denormals",
                 "light_inside_a_sphere", "light_on_a_triangle", "dir_oblique"):
         assert c.mask2.any()  # a finite light is hidden from some bounce point
@@ -301,38 +245,12 @@ def test_33_lights(pkg, oracle):
     hits, c = restated(oracle, "shadow_kinds", scene, sr.KINDS_W, sr.KINDS_H, rows)
     assert c.hit2.sum() >= 20 and c.at_p2.occluded[32].any() and c.at_p.occluded[32].any()
     compare(pkg, oracle, scene, hits, c, rows=rows, label="33 lights")  # the lit forms
-    with pytest.raises(pkg.RtError) as e:
-        pkg.shadow_hits_reflected(hits, scene, rows=rows)
-    assert e.value.status == pkg.RT_ERR_UNSUPPORTED
-    lib, sc, d = pkg.library(), scene.as_c(), np.array(REF_DIR, F32)
-    ctx = ctypes.c_void_p(d.ctypes.data)  # never used: the refusal comes first
-    buf = np.zeros(64, np.int32)
-    assert lib.rt_shadow_hits_reflected_device(ctx, buf.ctypes.data, ctypes.byref(sc),
-                                               d.ctypes.data, 2, 0, 2, buf.ctypes.data,
-                                               None) == pkg.RT_ERR_UNSUPPORTED
-    # 32 lights are served
-    scene32 = sr.kinds_scene(pkg, lights[:32])
-    assert pkg.shadow_hits_reflected(hits, scene32, rows=rows).shape == hits.shape
+    lc.more_than_32_lights(pkg, ENTRIES, scene, hits, rows)
 
 
 # --- 8. the argument contract ---------------------------------------------------------------------
 def test_object_out_of_range_is_refused(pkg):
-    scene = lr.with_lights(base(pkg), ONE_LIGHT)
-    hits = np.zeros((2, 3), pkg.HIT_DTYPE)
-    hits["t"] = 50.0
-    hits["object"] = 49  # the last slot
-    assert pkg.light_hits_shadowed_reflected(hits, scene, 0.5).shape == (2, 3, 4)
-    assert pkg.shadow_hits_reflected(hits, scene).shape == (2, 3)
-    for bad in (50, -2, 2**31 - 1, -2**31):
-        h = hits.copy()
-        h[1, 2]["object"] = bad
-        for call in (lambda: pkg.shadow_hits_reflected(h, scene),
-                     lambda: pkg.light_hits_shadowed_reflected(h, scene, 0.5),
-                     lambda: pkg.light_hits_shadowed_reflected(h, scene, 0.0),
-                     lambda: pkg.light_hits_shadowed_reflected(h, scene, 0.5, "rgba8")):
-            with pytest.raises(pkg.RtError) as e:
-                call()
-            assert e.value.status == pkg.RT_ERR_INVALID_ARG
+    lc.objects_out_of_range(pkg, ENTRIES)
 
 
 def test_reflectivity_outside_0_1_is_refused(pkg):
@@ -344,128 +262,24 @@ def test_reflectivity_outside_0_1_is_refused(pkg):
     for refl in (-0.1, 1.5, float("nan"), float(np.nextafter(F32(1), F32(2))), -1e-30,
                  float("inf")):
         for fmt in ("i32x4", "rgba8"):
-            with pytest.raises(pkg.RtError) as e:
-                pkg.light_hits_shadowed_reflected(hits, scene, refl, fmt)
-            assert e.value.status == pkg.RT_ERR_INVALID_ARG
+            lc.refused(pkg, lambda: pkg.light_hits_shadowed_reflected(hits, scene, refl, fmt))
 
 
 def test_formats_widths_rows_and_pointers_are_refused(pkg):
-    scene = base(pkg)
-    hits = np.zeros((4, 5), pkg.HIT_DTYPE)
-    hits["t"], hits["object"] = K_FAR, -1
-    with pytest.raises(ValueError):
-        pkg.light_hits_shadowed_reflected(hits, scene, 0.5, "hit")
-    with pytest.raises(ValueError):
-        pkg.light_hits_shadowed_reflected(hits, scene, 0.5, rows=(0, 3))  # four rows of hits
-    with pytest.raises(ValueError):
-        pkg.shadow_hits_reflected(hits, scene, rows=(0, 3))
-    with pytest.raises(ValueError):
-        pkg.shadow_hits_reflected(hits.reshape(-1), scene)
-    lib, sc, d = pkg.library(), scene.as_c(), np.array(REF_DIR, F32)
-    out = np.zeros((4, 5, 4), np.int32)
-    hp, dp, op, bad = hits.ctypes.data, d.ctypes.data, out.ctypes.data, pkg.RT_ERR_INVALID_ARG
-
-    def light(width, rb, re, fmt=0, refl=0.5, hits_p=hp, scene_p=ctypes.byref(sc), dir_p=dp,
-              out_p=op):
-        return lib.rt_light_hits_shadowed_reflected(hits_p, scene_p, dir_p, width, rb, re, refl,
-                                                    fmt, out_p)
-
-    def light0(width, rb, re, **kw):
-        return light(width, rb, re, refl=0.0, **kw)
-
-    def mask(width, rb, re, hits_p=hp, scene_p=ctypes.byref(sc), dir_p=dp, out_p=op):
-        return lib.rt_shadow_hits_reflected(hits_p, scene_p, dir_p, width, rb, re, out_p)
-
-    assert light(5, 0, 4) == 0 and light(5, 0, 4, 1) == 0 and mask(5, 0, 4) == 0
-    assert light0(5, 0, 4) == 0
-    assert light(5, 1 << 20, (1 << 20) + 4) == 0 and mask(5, 1 << 20, (1 << 20) + 4) == 0
-    for fmt in (2, 3, 4, -1):
-        assert light(5, 0, 4, fmt) == bad and light(5, 0, 4, fmt, refl=0.0) == bad
-    for fn in (light, light0, mask):
-        for width, rb, re in ((0, 0, 4), (-1, 0, 4), ((1 << 24) + 1, 0, 1), (5, -1, 3), (5, 4, 4),
-                              (5, 4, 3), (5, 1 << 24, (1 << 24) + 1)):
-            assert fn(width, rb, re) == bad, (fn.__name__, width, rb, re)
-        for kw in ("hits_p", "scene_p", "dir_p", "out_p"):
-            assert fn(5, 0, 4, **{kw: None}) == bad, (fn.__name__, kw)
-    # counts: negative, or an array missing for a non-zero count
-    for fields in ({"num_lights": -1}, {"num_lights": 1, "lights": None}, {"num_cubes": -1},
-                   {"num_spheres": -1}, {"cube_vertices": None}, {"sphere_origins": None}):
-        c = scene.as_c()
-        for field, value in fields.items():
-            setattr(c, field, value)
-        assert light(5, 0, 4, scene_p=ctypes.byref(c)) == bad, fields
-        assert mask(5, 0, 4, scene_p=ctypes.byref(c)) == bad, fields
+    lc.formats_widths_rows_and_pointers(pkg, ENTRIES)
 
 
 def test_device_entries_refuse_bad_arguments_before_any_hip_call(pkg):
-    """A NULL context, and with it every other refusal, comes before the
-    first HIP call: this runs without a GPU."""
-    lib, sc, d = pkg.library(), base(pkg).as_c(), np.array(REF_DIR, F32)
-    buf = np.zeros(64, np.int32)
-    p, bad = buf.ctypes.data, pkg.RT_ERR_INVALID_ARG
-    assert p % 16 == 0
-    assert lib.rt_shadow_hits_reflected_device(None, p, ctypes.byref(sc), d.ctypes.data, 2, 0, 2,
-                                               p, None) == bad
-    for fmt in (0, 1):
-        for refl in (0.0, 0.5):
-            assert lib.rt_light_hits_shadowed_reflected_device(
-                None, p, ctypes.byref(sc), d.ctypes.data, 2, 0, 2, refl, fmt, p, None) == bad
-    # with a context that is never used: misaligned and NULL pointers, r, the format
-    ctx = ctypes.c_void_p(buf.ctypes.data)
-
-    def mask(hits_p=p, out_p=p, width=2):
-        return lib.rt_shadow_hits_reflected_device(ctx, hits_p, ctypes.byref(sc), d.ctypes.data,
-                                                   width, 0, 2, out_p, None)
-
-    def light(fmt, refl=0.5, hits_p=p, out_p=p, width=2):
-        return lib.rt_light_hits_shadowed_reflected_device(
-            ctx, hits_p, ctypes.byref(sc), d.ctypes.data, width, 0, 2, refl, fmt, out_p, None)
-
-    assert mask(hits_p=p + 4) == bad and mask(out_p=p + 2) == bad
-    assert mask(hits_p=None) == bad and mask(out_p=None) == bad and mask(width=0) == bad
-    assert light(0, hits_p=p + 4) == bad and light(0, out_p=p + 8) == bad
-    assert light(1, out_p=p + 2) == bad and light(1, hits_p=None) == bad
-    assert light(0, width=0) == bad and light(1, width=(1 << 24) + 1) == bad
-    for refl in (-0.1, 1.5, float("nan")):
-        assert light(0, refl) == bad and light(1, refl) == bad
-    for fmt in (2, 3, -1):
-        assert light(fmt) == bad and light(fmt, 0.0) == bad
+    lc.device_entries_refuse_bad_arguments(pkg, ENTRIES)
 
 
 def test_python_names(pkg):
-    assert "shadow_hits_reflected" in pkg.__all__
-    assert "light_hits_shadowed_reflected" in pkg.__all__
-    for name in ("rt_shadow_hits_reflected", "rt_light_hits_shadowed_reflected",
-                 "rt_shadow_hits_reflected_device", "rt_light_hits_shadowed_reflected_device"):
-        assert name in pkg.EXPORTED_SYMBOLS and hasattr(pkg.library(), name)
-    assert list(inspect.signature(pkg.shadow_hits_reflected).parameters) == [
-        "hits", "scene", "rows", "ray_dir"]
-    assert list(inspect.signature(pkg.light_hits_shadowed_reflected).parameters) == [
-        "hits", "scene", "reflectivity", "fmt", "rows", "ray_dir"]
-    assert hasattr(pkg.RayTracer, "shadow_hits_reflected_device")
-    dev = inspect.signature(pkg.RayTracer.light_hits_reflected_device).parameters
-    assert list(dev)[-1] == "shadows" and dev["shadows"].default is False
-    assert list(dev)[:-1] == ["self", "hits_ptr", "device_scene", "width", "rows", "out_ptr",
-                              "reflectivity", "ray_dir", "stream", "fmt"]
-    assert pkg.library().rt_abi_version() == 1
+    lc.names(pkg, ENTRIES)
 
 
 # --- 9. under the sanitizers ----------------------------------------------------------------------
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_shadow_reflect_arguments_under_sanitizers(tmp_path):
-    """tests/shadow_reflect_args_check.cpp with csrc/rt_light.cpp and
-    csrc/rt_args.cpp under AddressSanitizer + UndefinedBehaviorSanitizer, run
-    as a program: exactly-sized heap arrays, the shadow term's scene, an empty
-    scene with NULL arrays, a band, the refusals."""
-    csrc = REPO / "opencl-ray-tracer_amd" / "csrc"
-    exe = tmp_path / "shadow_reflect_args_check"
-    subprocess.run(["g++", "-O1", "-g", "-ffp-contract=off", "-std=c++17",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    f"-I{REPO / 'include'}", "-o", str(exe),
-                    str(REPO / "tests" / "shadow_reflect_args_check.cpp"),
-                    str(csrc / "rt_light.cpp"), str(csrc / "rt_args.cpp"), "-lm"],
-                   check=True, capture_output=True, text=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr[-4000:]
-    assert "shadow reflect args check ok" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    """tests/shadow_reflect_args_check.cpp: exactly-sized heap arrays, the
+    shadow term's scene, an empty scene with NULL arrays, a band, the refusals."""
+    lc.run_args_check(tmp_path, "shadow_reflect")
