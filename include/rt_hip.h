@@ -576,6 +576,108 @@ int rt_light_hits_mirrored_device(rt_ctx* ctx, const rt_hit* device_hits,
                                   int32_t shadows, int32_t out_format, void* device_out,
                                   void* stream);
 
+/* ---- ray queries: the caller's own rays, and a camera --- */
+/* No reference counterpart (the reference traces its own orthographic grid
+ * and nothing else).  The two walks of the light pass, over rays the caller
+ * chose: a picking ray, a perspective view, ambient-occlusion or probe rays.
+ *
+ * rt_cast_rays*: per ray the closest hit from the origin o along the direction
+ * d (not normalised: the parameter is in units of |d|), over every object but
+ * `skip`: all twelve triangles of every cube (the reference's fp64 test on the
+ * doubles of o and d, a candidate iff it hits with td > 0, at (float)td), then
+ * every sphere (fp32, the quadratic of §3.1b: the near root where it is > 0,
+ * else the far one where that is > 0, so an origin inside a sphere gives its
+ * far side).  A candidate is taken iff it is strictly nearer than 300000 and
+ * everything before it, so ties go to the first in that order.  out_hits[i] is
+ * the parameter and the colour slot met, (300000, -1) for a miss;
+ * out_triangle, where it is not NULL, gets the cube triangle met (0..11), -1
+ * on a sphere or a miss.  This is rt_light::bounce_walk as it is: the bounce
+ * of rt_reflect_hits from a point and along a direction of the caller's.
+ * rt_occlude_rays*: one byte per ray, 1 iff some object other than `skip`
+ * cuts the open segment (o, o + d): a triangle at 0 < td < 1, a sphere with a
+ * root in (0, 1).  The segment's end is at parameter 1, so the caller scales
+ * d.  This is rt_light::light_occluded, the any-hit test of rt_shadow_hits.
+ *
+ * These are the secondary-ray tests: forward only, and the quadratic sphere.
+ * They are not the render's `collide`, which also takes triangles behind the
+ * origin (t < 0) and tests spheres through dot4 with w and tca: a cast of the
+ * library's own primary rays (rt_camera_reference) is NOT claimed to equal an
+ * RT_FORMAT_HIT frame.
+ *
+ * `skip` is compared and never used as an index.  The host functions refuse
+ * (RT_ERR_INVALID_ARG; the outputs may then be partly written) a skip outside
+ * [-1, num_cubes + num_spheres); a kernel returns no status and treats such an
+ * id as -1.  Nothing else about a ray is special: NaN, infinite or zero
+ * origins and directions fall out of the comparisons as "no candidate" and
+ * "not occluded", the same on host and device.
+ *
+ * A camera is affine in the pixel: pixel (x, y) has the origin
+ * (o0 + x * ou) + y * ov and the direction (d0 + x * du) + y * dv, per
+ * component in fp32 with x and y as floats (exact: width and rows are at most
+ * 2^24), and with `normalise` the direction divided by its length
+ * sqrtf((dx * dx + dy * dy) + dz * dz), three divisions.  That covers the
+ * orthographic grid and the pinhole.
+ * rt_camera_rays*: rows [row_begin, row_end) of a frame `width` wide as rays,
+ * row-major: ray i is pixel (i % width, row_begin + i / width), skip = -1,
+ * reserved = 0.
+ * rt_cast_camera*: word for word what rt_cast_rays* gives on those rays; on
+ * the device in one launch and without the ray buffer (32 bytes per pixel).
+ * rt_camera_reference: the library's own primary rays, origin (x, y, 0) and
+ * direction ray_dir.xyz, not normalised (a -0 component comes out of the
+ * camera's sum as +0).
+ * rt_camera_pinhole: a pinhole at `eye` looking at `target`, `fov_y_degrees`
+ * over the frame's height, square pixels; the direction goes through the
+ * CENTRE of pixel (x, y), row 0 at the top (towards `up`), x growing along
+ * cross(target - eye, up) (a right-handed view); normalise = 1.  Computed in double and rounded to float once; a convenience in front of
+ * the exact part, with no bit-exactness claim of its own.  RT_ERR_INVALID_ARG
+ * for NULL, a non-finite input, fov outside (0, 180), width or height < 1,
+ * eye == target, or `up` zero or parallel to the view.
+ *
+ * RT_ERR_INVALID_ARG: a NULL rays, scene, camera or output (out_triangle may
+ * be NULL), n < 0, normalise other than 0 or 1, the scene and band checks of
+ * rt_light_hits, a misaligned pointer (rays 16 bytes, hits 8, triangles 4).
+ * n == 0 is RT_OK and does nothing.  RT_ERR_UNSUPPORTED above 2^39 - 256 rays
+ * (one launch's grid, as in the light pass).  The outputs must not overlap
+ * `rays`; that is not checked.  Device calls: every array pointer is a device
+ * pointer (the rt_scene and rt_camera structs are read on the host during the
+ * call); everything above is checked before any HIP call; asynchronous on
+ * `stream` (NULL = the context's stream); one launch, no workspace, no
+ * allocation.  Host and device results are bit-identical. */
+typedef struct rt_ray {      /* 32 bytes; arrays of them 16-byte aligned */
+    float ox, oy, oz;        /* origin */
+    int32_t skip;            /* colour slot left out of the walk (cubes, then spheres), or -1 */
+    float dx, dy, dz;        /* direction, not normalised by the queries */
+    float reserved;          /* written 0 by rt_camera_rays*, never read */
+} rt_ray;
+
+typedef struct rt_camera {
+    float o0[3], ou[3], ov[3];   /* origin of pixel (x, y):    (o0 + x*ou) + y*ov */
+    float d0[3], du[3], dv[3];   /* direction of pixel (x, y): (d0 + x*du) + y*dv */
+    int32_t normalise;           /* 1: d = d / |d|, 0: as computed */
+} rt_camera;
+
+int rt_cast_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, rt_hit* out_hits,
+                 int32_t* out_triangle);
+int rt_occlude_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, uint8_t* out_occluded);
+int rt_camera_rays(const rt_camera* camera, int32_t width, int32_t row_begin, int32_t row_end,
+                   rt_ray* out_rays);
+int rt_cast_camera(const rt_camera* camera, const rt_scene* scene, int32_t width,
+                   int32_t row_begin, int32_t row_end, rt_hit* out_hits, int32_t* out_triangle);
+int rt_cast_rays_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                        const rt_scene* device_scene, rt_hit* device_out_hits,
+                        int32_t* device_out_triangle, void* stream);
+int rt_occlude_rays_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                           const rt_scene* device_scene, uint8_t* device_out_occluded,
+                           void* stream);
+int rt_camera_rays_device(rt_ctx* ctx, const rt_camera* camera, int32_t width, int32_t row_begin,
+                          int32_t row_end, rt_ray* device_out_rays, void* stream);
+int rt_cast_camera_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene* device_scene,
+                          int32_t width, int32_t row_begin, int32_t row_end,
+                          rt_hit* device_out_hits, int32_t* device_out_triangle, void* stream);
+int rt_camera_pinhole(const float eye[3], const float target[3], const float up[3],
+                      float fov_y_degrees, int32_t width, int32_t height, rt_camera* out);
+int rt_camera_reference(const float ray_dir[4], rt_camera* out);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

@@ -1,7 +1,8 @@
 /*
  * rt_internal.h -- shared between the library's own translation units
  * (rt_device.hip, rt_scene_device.hip and, through rt_light_device.inc,
- * rt_light.hip, rt_shadow.hip, rt_reflect.hip, rt_shadow_reflect.hip).  Not
+ * rt_light.hip, rt_shadow.hip, rt_reflect.hip, rt_shadow_reflect.hip,
+ * rt_rays.hip).  Not
  * installed, not part of the ABI.
  */
 #ifndef RT_INTERNAL_H
@@ -24,6 +25,8 @@ int preload_light_kernels();
 int preload_shadow_kernels();
 // ... and rt_reflect.hip's
 int preload_reflect_kernels();
+// ... and rt_rays.hip's
+int preload_rays_kernels();
 }  // namespace rt_internal
 
 #endif /* RT_INTERNAL_H */

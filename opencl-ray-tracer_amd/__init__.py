@@ -29,6 +29,7 @@ __all__ = [
     "shade_hits", "SURFACE_DTYPE", "hit_surfaces", "light_hits", "shadow_hits",
     "reflect_hits", "light_hits_reflected", "shadow_hits_reflected",
     "light_hits_shadowed_reflected", "RT_MAX_BOUNCES", "bounce_hits", "light_hits_mirrored",
+    "RAY_DTYPE", "Camera", "cast_rays", "occlude_rays", "camera_rays", "cast_camera",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -47,6 +48,10 @@ HIT_MISS_T = np.float32(300000.0)
 # rt_surface (include/rt_hip.h): one pixel of hit_surfaces: the unit normal
 # turned against the ray and the cube triangle hit (-1: sphere or miss).
 SURFACE_DTYPE = np.dtype([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("triangle", "<i4")])
+# rt_ray (include/rt_hip.h): one ray of cast_rays / occlude_rays: origin, the
+# colour slot left out of the walk (-1: none), direction (not normalised).
+RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("skip", "<i4"),
+                      ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("reserved", "<f4")])
 _PATHS = {"auto": RT_PATH_AUTO, "binned": RT_PATH_BINNED, "generic": RT_PATH_GENERIC}
 
 # Every symbol include/rt_hip.h declares (tests check the .so exports them).
@@ -65,6 +70,9 @@ EXPORTED_SYMBOLS = (
     "rt_light_hits_shadowed_reflected", "rt_shadow_hits_reflected_device",
     "rt_light_hits_shadowed_reflected_device", "rt_bounce_hits", "rt_bounce_hits_device",
     "rt_light_hits_mirrored", "rt_light_hits_mirrored_device",
+    "rt_cast_rays", "rt_occlude_rays", "rt_camera_rays", "rt_cast_camera", "rt_cast_rays_device",
+    "rt_occlude_rays_device", "rt_camera_rays_device", "rt_cast_camera_device",
+    "rt_camera_pinhole", "rt_camera_reference",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -98,6 +106,14 @@ class _Timing(ctypes.Structure):
         ("total_us", ctypes.c_double), ("upload_us", ctypes.c_double),
         ("kernel_us", ctypes.c_double), ("download_us", ctypes.c_double),
         ("path", ctypes.c_int32),
+    ]
+
+
+class _Camera(ctypes.Structure):
+    _fields_ = [
+        ("o0", ctypes.c_float * 3), ("ou", ctypes.c_float * 3), ("ov", ctypes.c_float * 3),
+        ("d0", ctypes.c_float * 3), ("du", ctypes.c_float * 3), ("dv", ctypes.c_float * 3),
+        ("normalise", ctypes.c_int32),
     ]
 
 
@@ -209,6 +225,22 @@ def library() -> ctypes.CDLL:
                                                   vp, i32, i32, i32, vp]),
         "rt_light_hits_mirrored_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, i32,
                                                          i32, i32, vp, i32, i32, i32, vp, vp]),
+        "rt_cast_rays": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp, vp]),
+        "rt_occlude_rays": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp]),
+        "rt_camera_rays": (ctypes.c_int, [ctypes.POINTER(_Camera), i32, i32, i32, vp]),
+        "rt_cast_camera": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.POINTER(_Scene), i32,
+                                          i32, i32, vp, vp]),
+        "rt_cast_rays_device": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp,
+                                               vp, vp]),
+        "rt_occlude_rays_device": (ctypes.c_int, [vp, vp, ctypes.c_int64, ctypes.POINTER(_Scene),
+                                                  vp, vp]),
+        "rt_camera_rays_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera), i32, i32, i32, vp,
+                                                 vp]),
+        "rt_cast_camera_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera),
+                                                 ctypes.POINTER(_Scene), i32, i32, i32, vp, vp,
+                                                 vp]),
+        "rt_camera_pinhole": (ctypes.c_int, [vp, vp, vp, f32, i32, i32, ctypes.POINTER(_Camera)]),
+        "rt_camera_reference": (ctypes.c_int, [vp, ctypes.POINTER(_Camera)]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -652,6 +684,130 @@ def light_hits_mirrored(hits: np.ndarray, scene: Scene, reflectivity, max_bounce
     return out
 
 
+def _vec3(v) -> np.ndarray:
+    a = np.ascontiguousarray(v, np.float32).reshape(-1)
+    if a.size != 3:
+        raise ValueError(f"a camera vector holds three floats, got {a.size}")
+    return a
+
+
+@dataclass
+class Camera:
+    """rt_camera (include/rt_hip.h): an affine camera.  Pixel (x, y) has the
+    origin (o0 + x * ou) + y * ov and the direction (d0 + x * du) + y * dv, in
+    float32, divided by its length where `normalise` is 1."""
+
+    o0: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    ou: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    ov: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    d0: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    du: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    dv: np.ndarray = field(default_factory=lambda: np.zeros(3, np.float32))
+    normalise: int = 0
+
+    _VECTORS = ("o0", "ou", "ov", "d0", "du", "dv")
+
+    def __post_init__(self):
+        for name in self._VECTORS:
+            setattr(self, name, _vec3(getattr(self, name)))
+        self.normalise = int(self.normalise)
+
+    def as_c(self) -> _Camera:
+        c = _Camera()
+        for name in self._VECTORS:
+            getattr(c, name)[:] = [float(x) for x in getattr(self, name)]
+        c.normalise = self.normalise
+        return c
+
+    @classmethod
+    def _from_c(cls, c: _Camera) -> "Camera":
+        return cls(*[np.array(getattr(c, name)[:], np.float32) for name in cls._VECTORS],
+                   int(c.normalise))
+
+    @classmethod
+    def pinhole(cls, eye, target, up, fov_y: float, width: int, height: int) -> "Camera":
+        """rt_camera_pinhole: a pinhole at `eye` looking at `target`, `fov_y`
+        degrees over the frame's height, the ray through the centre of every
+        pixel, row 0 at the top (towards `up`), unit directions."""
+        c = _Camera()
+        e, t, u = _vec3(eye), _vec3(target), _vec3(up)
+        _check(library().rt_camera_pinhole(_ptr(e), _ptr(t), _ptr(u), fov_y, width, height,
+                                           ctypes.byref(c)), "rt_camera_pinhole")
+        return cls._from_c(c)
+
+    @classmethod
+    def reference(cls, ray_dir: Optional[np.ndarray] = None) -> "Camera":
+        """rt_camera_reference: the library's own primary rays, origin
+        (x, y, 0) and direction ray_dir.xyz, not normalised."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        if d.size != 4:
+            raise ValueError("ray_dir holds four floats")
+        c = _Camera()
+        _check(library().rt_camera_reference(_ptr(d), ctypes.byref(c)), "rt_camera_reference")
+        return cls._from_c(c)
+
+
+def _rays(rays: np.ndarray) -> np.ndarray:
+    rays = np.ascontiguousarray(rays)
+    if rays.dtype != RAY_DTYPE:
+        raise ValueError(f"rays must be a RAY_DTYPE array, got {rays.dtype}")
+    return rays
+
+
+def cast_rays(rays: np.ndarray, scene: Scene, triangles: bool = False):
+    """rt_cast_rays: per ray (RAY_DTYPE, any shape) the closest hit from its
+    origin along its direction over every object of `scene` but its `skip`, as
+    a HIT_DTYPE array of the same shape: the parameter along the (un-normalised)
+    direction and the colour slot, (HIT_MISS_T, -1) for a miss.
+    triangles=True: (hits, int32 array of the cube triangle met, -1 on a
+    sphere or a miss).  On the host."""
+    rays = _rays(rays)
+    out = np.empty(rays.shape, HIT_DTYPE)
+    tri = np.empty(rays.shape, np.int32) if triangles else None
+    sc = scene.as_c()
+    _check(library().rt_cast_rays(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(out), _ptr(tri)),
+           "rt_cast_rays")
+    return (out, tri) if triangles else out
+
+
+def occlude_rays(rays: np.ndarray, scene: Scene) -> np.ndarray:
+    """rt_occlude_rays: per ray a uint8, 1 iff an object of `scene` other than
+    its `skip` cuts the open segment from its origin to origin + direction.
+    On the host."""
+    rays = _rays(rays)
+    out = np.empty(rays.shape, np.uint8)
+    sc = scene.as_c()
+    _check(library().rt_occlude_rays(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(out)),
+           "rt_occlude_rays")
+    return out
+
+
+def camera_rays(camera: Camera, width: int, height: int,
+                rows: Optional[Tuple[int, int]] = None) -> np.ndarray:
+    """rt_camera_rays: the rays of `camera` over a width x height frame (or its
+    `rows`) as a (rows x width) RAY_DTYPE array, skip = -1.  On the host."""
+    rb, re = rows if rows is not None else (0, height)
+    out = np.empty((max(re - rb, 0), max(width, 0)), RAY_DTYPE)
+    c = camera.as_c()
+    _check(library().rt_camera_rays(ctypes.byref(c), width, rb, re, _ptr(out)), "rt_camera_rays")
+    return out
+
+
+def cast_camera(camera: Camera, scene: Scene, width: int, height: int,
+                rows: Optional[Tuple[int, int]] = None, triangles: bool = False):
+    """rt_cast_camera: cast_rays on camera_rays' rays, without the rays: a
+    (rows x width) HIT_DTYPE frame (with triangles=True, and the int32
+    triangles).  On the host."""
+    rb, re = rows if rows is not None else (0, height)
+    shape = (max(re - rb, 0), max(width, 0))
+    out = np.empty(shape, HIT_DTYPE)
+    tri = np.empty(shape, np.int32) if triangles else None
+    c, sc = camera.as_c(), scene.as_c()
+    _check(library().rt_cast_camera(ctypes.byref(c), ctypes.byref(sc), width, rb, re, _ptr(out),
+                                    _ptr(tri)), "rt_cast_camera")
+    return (out, tri) if triangles else out
+
+
 def _device_scene(device_scene: dict) -> _Scene:
     """rt_scene of device addresses, lights included (hit post-passes)."""
     g = device_scene.get
@@ -863,6 +1019,48 @@ class RayTracer:
             self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
             reflectivity_ptr or None, int(max_bounces), int(shadows), _FORMATS[fmt],
             out_ptr or None, stream or None), "rt_light_hits_mirrored_device")
+
+    def cast_rays_device(self, rays_ptr: int, n: int, device_scene: dict, hits_ptr: int,
+                         triangles_ptr: int = 0, stream: int = 0) -> None:
+        """rt_cast_rays_device: `n` rt_ray records at the device address
+        `rays_ptr` (16-byte aligned) to rt_hit records at `hits_ptr` (8-byte
+        aligned) and, where `triangles_ptr` is given, one int32 triangle per
+        ray.  The outputs must not overlap the rays.  Asynchronous on
+        `stream`.  `device_scene` as for render_device."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_cast_rays_device(self._ctx, rays_ptr or None, n, ctypes.byref(sc),
+                                             hits_ptr or None, triangles_ptr or None,
+                                             stream or None), "rt_cast_rays_device")
+
+    def occlude_rays_device(self, rays_ptr: int, n: int, device_scene: dict, out_ptr: int,
+                            stream: int = 0) -> None:
+        """rt_occlude_rays_device: `n` device rays to one uint8 per ray at
+        `out_ptr`.  Asynchronous on `stream`."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_occlude_rays_device(self._ctx, rays_ptr or None, n, ctypes.byref(sc),
+                                                out_ptr or None, stream or None),
+               "rt_occlude_rays_device")
+
+    def camera_rays_device(self, camera: Camera, width: int, rows: Tuple[int, int], out_ptr: int,
+                           stream: int = 0) -> None:
+        """rt_camera_rays_device: rows [rows[0], rows[1]) of `camera`'s frame
+        as rt_ray records at the device address `out_ptr` (16-byte aligned).
+        Asynchronous on `stream`."""
+        c = camera.as_c()
+        _check(library().rt_camera_rays_device(self._ctx, ctypes.byref(c), width, rows[0], rows[1],
+                                               out_ptr or None, stream or None),
+               "rt_camera_rays_device")
+
+    def cast_camera_device(self, camera: Camera, device_scene: dict, width: int,
+                           rows: Tuple[int, int], hits_ptr: int, triangles_ptr: int = 0,
+                           stream: int = 0) -> None:
+        """rt_cast_camera_device: cast_rays_device on camera_rays_device's
+        rays in one launch, without the ray buffer.  Asynchronous on `stream`."""
+        c, sc = camera.as_c(), _device_scene(device_scene)
+        _check(library().rt_cast_camera_device(self._ctx, ctypes.byref(c), ctypes.byref(sc), width,
+                                               rows[0], rows[1], hits_ptr or None,
+                                               triangles_ptr or None, stream or None),
+               "rt_cast_camera_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,

@@ -437,6 +437,7 @@ int rt_init(int device_ordinal, rt_ctx** out_ctx) {
         rt_internal::preload_light_kernels() != RT_OK ||
         rt_internal::preload_shadow_kernels() != RT_OK ||
         rt_internal::preload_reflect_kernels() != RT_OK ||
+        rt_internal::preload_rays_kernels() != RT_OK ||
         hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(grid_check_kernel)) !=
             hipSuccess) {
         rt_destroy(ctx);

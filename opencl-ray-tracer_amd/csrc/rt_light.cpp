@@ -6,7 +6,11 @@
 // the argument check they share with the device entry points (the launch of
 // rt_light_device.inc, for rt_light.hip, rt_shadow.hip, rt_reflect.hip and
 // rt_shadow_reflect.hip; rt_mirror.hip's own).  One pixel loop, run(); each function is its
-// argument checks and the per-pixel call it hands to the loop.
+// argument checks and the per-pixel call it hands to the loop.  Behind them the
+// ray queries, rt_cast_rays / rt_occlude_rays /
+// rt_camera_rays / rt_cast_camera: plain loops over bounce_walk, light_occluded
+// and the camera text of include/rt_rays_impl.h, and the checks they share with
+// rt_rays.hip.
 // Plain C++, no HIP.  The arithmetic is include/rt_light_impl.h, the text the
 // kernel compiles too; built with -ffp-contract=off like rt_scene.cpp.
 #include <cstring>
@@ -15,6 +19,7 @@
 #include "rt_args.h"
 #include "rt_hip.h"
 #include "rt_light_impl.h"
+#include "rt_rays_impl.h"
 
 namespace rt_light {
 
@@ -26,6 +31,38 @@ int check(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32
         return RT_ERR_INVALID_ARG;
     if (scene->num_lights > 0 && !scene->lights) return RT_ERR_INVALID_ARG;
     return RT_OK;
+}
+
+namespace {
+bool misaligned(const void* p, uintptr_t align) {
+    return reinterpret_cast<uintptr_t>(p) % align != 0;
+}
+}  // namespace
+
+int check_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, const void* out,
+               uintptr_t out_align, const int32_t* triangle) {
+    if (!rays || !scene || !out || n < 0) return RT_ERR_INVALID_ARG;
+    // the scene alone: rt_render's counts and arrays, on a frame of one pixel
+    if (rt_args::check_args(scene, 1, 1, 0, 1, RT_FORMAT_I32X4)) return RT_ERR_INVALID_ARG;
+    if (scene->num_lights > 0 && !scene->lights) return RT_ERR_INVALID_ARG;
+    if (misaligned(rays, 16) || misaligned(out, out_align) || misaligned(triangle, 4))
+        return RT_ERR_INVALID_ARG;
+    return n > kMaxRays ? RT_ERR_UNSUPPORTED : RT_OK;
+}
+
+int check_camera(const rt_camera* camera, const rt_scene* scene, bool with_scene, int32_t width,
+                 int32_t row_begin, int32_t row_end, const void* out, uintptr_t out_align,
+                 const int32_t* triangle) {
+    if (!camera || !out || (with_scene && !scene)) return RT_ERR_INVALID_ARG;
+    if (camera->normalise != 0 && camera->normalise != 1) return RT_ERR_INVALID_ARG;
+    const rt_scene none{};  // rt_camera_rays: the band checks alone
+    const rt_scene* s = with_scene ? scene : &none;
+    if (rt_args::check_args(s, width, row_end, row_begin, row_end, RT_FORMAT_I32X4))
+        return RT_ERR_INVALID_ARG;
+    if (s->num_lights > 0 && !s->lights) return RT_ERR_INVALID_ARG;
+    if (misaligned(out, out_align) || misaligned(triangle, 4)) return RT_ERR_INVALID_ARG;
+    return static_cast<int64_t>(row_end - row_begin) * width > kMaxRays ? RT_ERR_UNSUPPORTED
+                                                                        : RT_OK;
 }
 
 namespace {
@@ -76,6 +113,70 @@ int run(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32_t
 extern "C" {
 
 using namespace rt_light;
+
+// ---- the ray queries -------------------------------------------
+
+// The closest hit of every ray: bounce_walk from o along d, `skip` left out.
+int rt_cast_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, rt_hit* out_hits,
+                 int32_t* out_triangle) {
+    const int rc = check_rays(rays, n, scene, out_hits, sizeof(rt_hit), out_triangle);
+    if (rc) return rc;
+    const rt_scene& s = *scene;
+    for (int64_t i = 0; i < n; ++i) {
+        const rt_ray& r = rays[i];
+        if (ray_skip(s, r.skip) != r.skip) return RT_ERR_INVALID_ARG;
+        const Bounce b = bounce_walk(s, r.skip, Vec3{r.ox, r.oy, r.oz}, Vec3{r.dx, r.dy, r.dz});
+        out_hits[i] = rt_hit{b.best, b.obj2};
+        if (out_triangle) out_triangle[i] = b.tri2;
+    }
+    return RT_OK;
+}
+
+// Is the open segment (o, o + d) of every ray cut: light_occluded, `skip` left out.
+int rt_occlude_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, uint8_t* out_occluded) {
+    const int rc = check_rays(rays, n, scene, out_occluded, 1, nullptr);
+    if (rc) return rc;
+    const rt_scene& s = *scene;
+    for (int64_t i = 0; i < n; ++i) {
+        const rt_ray& r = rays[i];
+        if (ray_skip(s, r.skip) != r.skip) return RT_ERR_INVALID_ARG;
+        out_occluded[i] =
+            light_occluded(s, r.skip, Vec3{r.ox, r.oy, r.oz}, Vec3{r.dx, r.dy, r.dz}) ? 1 : 0;
+    }
+    return RT_OK;
+}
+
+// The rays of a band of a camera's frame, row-major.
+int rt_camera_rays(const rt_camera* camera, int32_t width, int32_t row_begin, int32_t row_end,
+                   rt_ray* out_rays) {
+    const int rc =
+        check_camera(camera, nullptr, false, width, row_begin, row_end, out_rays, 16, nullptr);
+    if (rc) return rc;
+    int64_t i = 0;
+    for (int32_t y = row_begin; y < row_end; ++y)
+        for (int32_t x = 0; x < width; ++x, ++i) {
+            const Ray r = camera_ray(*camera, static_cast<float>(x), static_cast<float>(y));
+            out_rays[i] = rt_ray{r.o.x, r.o.y, r.o.z, -1, r.d.x, r.d.y, r.d.z, 0.0f};
+        }
+    return RT_OK;
+}
+
+// rt_cast_rays on rt_camera_rays' rays, without the rays.
+int rt_cast_camera(const rt_camera* camera, const rt_scene* scene, int32_t width,
+                   int32_t row_begin, int32_t row_end, rt_hit* out_hits, int32_t* out_triangle) {
+    const int rc = check_camera(camera, scene, true, width, row_begin, row_end, out_hits,
+                                sizeof(rt_hit), out_triangle);
+    if (rc) return rc;
+    int64_t i = 0;
+    for (int32_t y = row_begin; y < row_end; ++y)
+        for (int32_t x = 0; x < width; ++x, ++i) {
+            const Ray r = camera_ray(*camera, static_cast<float>(x), static_cast<float>(y));
+            const Bounce b = bounce_walk(*scene, -1, r.o, r.d);
+            out_hits[i] = rt_hit{b.best, b.obj2};
+            if (out_triangle) out_triangle[i] = b.tri2;
+        }
+    return RT_OK;
+}
 
 // The geometry of one bounce of the mirror chain.
 int rt_bounce_hits(const rt_hit* hits, const rt_scene* scene, const float ray_dir[4],

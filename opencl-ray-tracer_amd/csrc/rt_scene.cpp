@@ -409,6 +409,58 @@ uint64_t rt_fnv1a64(const void* words, int64_t n_words, uint64_t basis) {
     return h;
 }
 
+// The library's own primary rays as a camera: origin
+// (x, y, 0), direction ray_dir.xyz as it is.
+int rt_camera_reference(const float ray_dir[4], rt_camera* out) {
+    if (!ray_dir || !out) return RT_ERR_INVALID_ARG;
+    *out = rt_camera{};
+    out->ou[0] = 1.0f;
+    out->ov[1] = 1.0f;
+    for (int a = 0; a < 3; ++a) out->d0[a] = ray_dir[a];
+    out->normalise = 0;
+    return RT_OK;
+}
+
+// A pinhole camera in double, rounded to float once: the view f, x along
+// r = f x up, rows against u = r x f, and through the centre of pixel (x, y)
+// the direction f + sx * r + sy * u with sx = (2 (x + 1/2) / w - 1) * tan(fov / 2) * w / h
+// and sy = (1 - 2 (y + 1/2) / h) * tan(fov / 2): affine in x and y.
+int rt_camera_pinhole(const float eye[3], const float target[3], const float up[3],
+                      float fov_y_degrees, int32_t width, int32_t height, rt_camera* out) {
+    if (!eye || !target || !up || !out || width < 1 || height < 1) return RT_ERR_INVALID_ARG;
+    if (!(fov_y_degrees > 0.0f && fov_y_degrees < 180.0f)) return RT_ERR_INVALID_ARG;  // NaN too
+    double f[3], upd[3];
+    for (int a = 0; a < 3; ++a) {
+        if (!std::isfinite(eye[a]) || !std::isfinite(target[a]) || !std::isfinite(up[a]))
+            return RT_ERR_INVALID_ARG;
+        f[a] = static_cast<double>(target[a]) - static_cast<double>(eye[a]);
+        upd[a] = up[a];
+    }
+    const double fl = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+    const double ul = std::sqrt(upd[0] * upd[0] + upd[1] * upd[1] + upd[2] * upd[2]);
+    if (!(fl > 0.0) || !(ul > 0.0)) return RT_ERR_INVALID_ARG;  // eye == target, up == 0
+    for (int a = 0; a < 3; ++a) f[a] /= fl, upd[a] /= ul;
+    double r[3] = {f[1] * upd[2] - f[2] * upd[1], f[2] * upd[0] - f[0] * upd[2],
+                   f[0] * upd[1] - f[1] * upd[0]};
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    if (!(rl > 1e-9)) return RT_ERR_INVALID_ARG;  // up parallel to the view
+    for (int a = 0; a < 3; ++a) r[a] /= rl;
+    const double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2],
+                         r[0] * f[1] - r[1] * f[0]};
+    const double th = std::tan(static_cast<double>(fov_y_degrees) * (3.14159265358979323846 / 360.0));
+    const double tw = th * static_cast<double>(width) / static_cast<double>(height);
+    *out = rt_camera{};
+    for (int a = 0; a < 3; ++a) {
+        out->o0[a] = eye[a];
+        out->d0[a] = static_cast<float>(f[a] + (1.0 / width - 1.0) * tw * r[a] +
+                                        (1.0 - 1.0 / height) * th * u[a]);
+        out->du[a] = static_cast<float>(2.0 / width * tw * r[a]);
+        out->dv[a] = static_cast<float>(-2.0 / height * th * u[a]);
+    }
+    out->normalise = 1;
+    return RT_OK;
+}
+
 int rt_abi_version(void) { return RT_ABI_VERSION; }
 
 }  // extern "C"

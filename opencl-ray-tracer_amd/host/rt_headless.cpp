@@ -11,7 +11,17 @@
 //               [--synthetic N M k] [--rows A B] [--ppm out.ppm] [--repeat R]
 //               [--bands B] [--devices D] [--device-scene]
 //               [--format i32x4|rgba8|hit] [--throughput F [--inflight S]]
-//               [--known-answer] [--pick X,Y]
+//               [--known-answer] [--pick X,Y] [--camera EX,EY,EZ,TX,TY,TZ,FOVY]
+//
+// --camera (one band, no --device-scene / --throughput): a perspective view
+// instead of the reference's orthographic one.  A pinhole at (EX, EY, EZ)
+// looking at (TX, TY, TZ), FOVY degrees over the frame's height, up =
+// (0, -1, 0) so that row 0 is at the top of the scene's y-down frame
+// (rt_camera_pinhole); the scene is uploaded, rt_cast_camera_device casts one
+// ray per pixel of the rendered rows, the hit frame is read back and, for
+// --format i32x4 / rgba8, shaded on the host with rt_shade_hits; hash, --pick
+// and --ppm then see that frame as they see a render's.  These are the ray
+// queries' forward-only tests (rt_hip.h), not the render's `collide`.
 //
 // --known-answer (reference scene 1, 2 or 3, 640x480, int32x4, the whole
 // frame, seed 1): checks the frame against the reference's own CPU frame as
@@ -157,6 +167,50 @@ int render_device_scene(Band& band, int width, int height, int row_begin, int ro
     return status;
 }
 
+// --camera: the scene uploaded, one rt_cast_camera_device launch over the
+// band's rows, the hit frame read back and shaded into `pixels` (`fmt`).
+int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int width,
+                  int32_t fmt, std::vector<int32_t>& pixels) {
+    const size_t px = (size_t)width * (size_t)(band.row_end - band.row_begin);
+    const size_t ns = (size_t)scene.num_spheres, nc = (size_t)scene.num_cubes;
+    float *so = nullptr, *sr = nullptr, *sc = nullptr, *cv = nullptr, *cc = nullptr;
+    rt_hit* out = nullptr;
+    std::vector<rt_hit> hits(px);
+    auto upload = [](float** dev, const float* host, size_t floats) {
+        if (floats == 0) return true;  // (an empty array stays NULL)
+        return hipMalloc(dev, floats * sizeof(float)) == hipSuccess &&
+               hipMemcpy(*dev, host, floats * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    int status = 1;
+    if (upload(&so, scene.sphere_origins, 4 * ns) && upload(&sr, scene.sphere_radius, ns) &&
+        upload(&sc, scene.sphere_colours, 4 * ns) && upload(&cv, scene.cube_vertices, 144 * nc) &&
+        upload(&cc, scene.cube_colours, 4 * nc) &&
+        hipMalloc(&out, px * sizeof(rt_hit)) == hipSuccess) {
+        const rt_scene dev{so, sr, sc, scene.num_spheres, cv, cc, scene.num_cubes, nullptr, 0};
+        int rc = rt_cast_camera_device(band.ctx, &cam, &dev, width, band.row_begin, band.row_end,
+                                       out, nullptr, nullptr);
+        if (rc == RT_OK && (hipDeviceSynchronize() != hipSuccess ||
+                            hipMemcpy(hits.data(), out, px * sizeof(rt_hit),
+                                      hipMemcpyDeviceToHost) != hipSuccess))
+            rc = RT_ERR_HIP;
+        if (rc == RT_OK) {
+            if (fmt == RT_FORMAT_HIT)
+                std::memcpy(pixels.data(), hits.data(), px * sizeof(rt_hit));
+            else
+                rc = rt_shade_hits(hits.data(), (int64_t)px, &scene, fmt, pixels.data());
+        }
+        if (rc == RT_OK)
+            status = 0;
+        else
+            std::fprintf(stderr, "camera cast failed: %s\n", rt_error_string(rc));
+    } else {
+        std::fprintf(stderr, "scene upload failed\n");
+    }
+    for (void* p : {(void*)so, (void*)sr, (void*)sc, (void*)cv, (void*)cc, (void*)out})
+        if (p) (void)hipFree(p);
+    return status;
+}
+
 // --throughput: S slots round-robin over `frames` timed frames.
 int throughput(int device, int width, int height, int n, int m, unsigned seed, float k,
                const float ray_dir[4], int32_t fmt, int frames, int slots) {
@@ -273,6 +327,8 @@ int main(int argc, char** argv) {
     int32_t fmt = RT_FORMAT_I32X4;
     bool known_answer = false;
     int pick_x = -1, pick_y = -1;
+    bool camera = false;
+    float cam_v[7] = {};
     std::string ppm;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -318,6 +374,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (a == "--camera") {
+            camera = std::sscanf(next(), "%f,%f,%f,%f,%f,%f,%f", &cam_v[0], &cam_v[1], &cam_v[2],
+                                 &cam_v[3], &cam_v[4], &cam_v[5], &cam_v[6]) == 7;
+            if (!camera) {
+                std::fprintf(stderr, "--camera takes EX,EY,EZ,TX,TY,TZ,FOVY\n");
+                return 2;
+            }
+        }
         else {
             std::fprintf(stderr, "unknown option %s\n", a.c_str());
             return 2;
@@ -344,6 +408,17 @@ int main(int argc, char** argv) {
     if (device_scene && (syn_n < 0 || n_bands != 1)) {
         std::fprintf(stderr, "--device-scene needs --synthetic and one band\n");
         return 2;
+    }
+    rt_camera cam{};
+    if (camera) {
+        const float up[3] = {0.0f, -1.0f, 0.0f};
+        if (n_bands != 1 || device_scene || tp_frames > 0 || known_answer || repeat != 1 ||
+            rt_camera_pinhole(cam_v, cam_v + 3, up, cam_v[6], width, height, &cam) != RT_OK) {
+            std::fprintf(stderr, "--camera needs one band, no --device-scene, --throughput, "
+                                 "--known-answer or --repeat, eye != target, a view that is not "
+                                 "vertical and 0 < FOVY < 180\n");
+            return 2;
+        }
     }
     if (tp_frames > 0) {
         if (syn_n < 0 || n_bands != 1 || tp_slots < 1 || tp_slots > 8 || row_begin != 0 ||
@@ -413,7 +488,15 @@ int main(int argc, char** argv) {
     for (Band& band : bands) ctxs.push_back(band.ctx);
     std::vector<rt_timing> timings((size_t)n_bands);
     int status = 0;
-    for (int r = 0; r < repeat && status == 0; ++r) {
+    if (camera) {
+        std::printf("HIP Ray Tracer Begin\n");
+        status = render_camera(bands[0], scene, cam, width, fmt, pixels);
+        if (status == 0)
+            std::printf("camera eye (%g, %g, %g) target (%g, %g, %g) fov %g: one ray per pixel\n",
+                        (double)cam_v[0], (double)cam_v[1], (double)cam_v[2], (double)cam_v[3],
+                        (double)cam_v[4], (double)cam_v[5], (double)cam_v[6]);
+    }
+    for (int r = 0; r < repeat && status == 0 && !camera; ++r) {
         std::printf("HIP Ray Tracer Begin\n");
         rc = rt_render_multi(ctxs.data(), n_bands, &scene, ray_dir, nullptr, width, height,
                              row_begin, row_end, fmt, pixels.data(), timings.data());
