@@ -678,6 +678,69 @@ int rt_camera_pinhole(const float eye[3], const float target[3], const float up[
                       float fov_y_degrees, int32_t width, int32_t height, rt_camera* out);
 int rt_camera_reference(const float ray_dir[4], rt_camera* out);
 
+/* ---- culled ray queries from prebuilt cube bounds ------- */
+/* The ray queries above test every ray against all twelve triangles of every
+ * cube.  A caller may build one small record per cube once per scene and pass
+ * it to the *_accel forms of the three queries: a cube whose record proves
+ * that none of its triangles can be accepted for a ray is left out for that
+ * ray.  The results are the unculled calls' results word for word, on every
+ * input: the keep test (rt_light::cube_kept) allows for the
+ * rounding of the exact fp64 triangle test and keeps a cube whenever a miss is
+ * not proven, always for a non-finite ray, for a cube with a non-finite
+ * vertex, and for a ray within rounding of grazing one of the cube's
+ * triangles.  Spheres are not culled.
+ *
+ * rt_cube_bound: lo / hi are the exact minimum / maximum of the cube's 36
+ * vertices' x, y, z (w ignored); emax2 is the largest squared length of the 24
+ * edges v1 - v0 and v2 - v0 of its twelve triangles, computed in double and
+ * rounded up to float; normal[k] is e1 x e2 of triangle k in double.  A cube
+ * with a non-finite vertex coordinate has lo = -inf, hi = +inf, emax2 = +inf
+ * and zero normals.  A record is a function of its cube's vertices alone.
+ * rt_accel_build*: out[j] for every cube j of the scene.  Host and device
+ * records are bit-identical.  Rebuild after any change of cube_vertices.
+ * rt_*_accel*: the unculled call's arguments and contract, plus `accel`:
+ * num_cubes records as rt_accel_build* wrote them for THIS scene's vertices.
+ * A stale or foreign accel is not detectable and gives wrong results.
+ * rt_accel_kept: per ray the number of cubes other than its `skip` that the
+ * keep test keeps (segment = 0: the cast's test, 1: the occlusion test's).
+ *
+ * RT_ERR_INVALID_ARG: what the unculled call refuses; a NULL scene or, with
+ * num_cubes > 0, a NULL or misaligned (16 bytes) accel / out; segment other
+ * than 0 or 1; a NULL out_count.  num_cubes == 0: RT_OK, accel and out may be
+ * NULL, the build launches nothing.  Device calls: checked before any HIP
+ * call; asynchronous on `stream`; one launch, no workspace, no allocation. */
+typedef struct rt_cube_bound { /* 320 bytes; arrays of them 16-byte aligned */
+    float lo[3];
+    float emax2;
+    float hi[3];
+    float reserved;            /* 0 */
+    double normal[12][3];
+} rt_cube_bound;
+
+int rt_accel_build(const rt_scene* scene, rt_cube_bound* out);
+int rt_accel_build_device(rt_ctx* ctx, const rt_scene* device_scene, rt_cube_bound* device_out,
+                          void* stream);
+int rt_accel_kept(const rt_ray* rays, int64_t n, const rt_scene* scene,
+                  const rt_cube_bound* accel, int32_t segment, int32_t* out_count);
+int rt_cast_rays_accel(const rt_ray* rays, int64_t n, const rt_scene* scene,
+                       const rt_cube_bound* accel, rt_hit* out_hits, int32_t* out_triangle);
+int rt_occlude_rays_accel(const rt_ray* rays, int64_t n, const rt_scene* scene,
+                          const rt_cube_bound* accel, uint8_t* out_occluded);
+int rt_cast_camera_accel(const rt_camera* camera, const rt_scene* scene,
+                         const rt_cube_bound* accel, int32_t width, int32_t row_begin,
+                         int32_t row_end, rt_hit* out_hits, int32_t* out_triangle);
+int rt_cast_rays_accel_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                              const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                              rt_hit* device_out_hits, int32_t* device_out_triangle,
+                              void* stream);
+int rt_occlude_rays_accel_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                                 const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                                 uint8_t* device_out_occluded, void* stream);
+int rt_cast_camera_accel_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene* device_scene,
+                                const rt_cube_bound* device_accel, int32_t width,
+                                int32_t row_begin, int32_t row_end, rt_hit* device_out_hits,
+                                int32_t* device_out_triangle, void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

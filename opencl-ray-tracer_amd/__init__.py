@@ -30,6 +30,8 @@ __all__ = [
     "reflect_hits", "light_hits_reflected", "shadow_hits_reflected",
     "light_hits_shadowed_reflected", "RT_MAX_BOUNCES", "bounce_hits", "light_hits_mirrored",
     "RAY_DTYPE", "Camera", "cast_rays", "occlude_rays", "camera_rays", "cast_camera",
+    "CUBE_BOUND_DTYPE", "build_accel", "accel_kept", "cast_rays_accel", "occlude_rays_accel",
+    "cast_camera_accel",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -52,6 +54,10 @@ SURFACE_DTYPE = np.dtype([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("triangl
 # colour slot left out of the walk (-1: none), direction (not normalised).
 RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("skip", "<i4"),
                       ("dx", "<f4"), ("dy", "<f4"), ("dz", "<f4"), ("reserved", "<f4")])
+# rt_cube_bound (include/rt_hip.h): one cube's record of build_accel, for the
+# *_accel ray queries: its box, its largest squared edge, its triangles' normals.
+CUBE_BOUND_DTYPE = np.dtype([("lo", "<f4", (3,)), ("emax2", "<f4"), ("hi", "<f4", (3,)),
+                             ("reserved", "<f4"), ("normal", "<f8", (12, 3))])
 _PATHS = {"auto": RT_PATH_AUTO, "binned": RT_PATH_BINNED, "generic": RT_PATH_GENERIC}
 
 # Every symbol include/rt_hip.h declares (tests check the .so exports them).
@@ -73,6 +79,9 @@ EXPORTED_SYMBOLS = (
     "rt_cast_rays", "rt_occlude_rays", "rt_camera_rays", "rt_cast_camera", "rt_cast_rays_device",
     "rt_occlude_rays_device", "rt_camera_rays_device", "rt_cast_camera_device",
     "rt_camera_pinhole", "rt_camera_reference",
+    "rt_accel_build", "rt_accel_build_device", "rt_accel_kept", "rt_cast_rays_accel",
+    "rt_occlude_rays_accel", "rt_cast_camera_accel", "rt_cast_rays_accel_device",
+    "rt_occlude_rays_accel_device", "rt_cast_camera_accel_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -241,6 +250,22 @@ def library() -> ctypes.CDLL:
                                                  vp]),
         "rt_camera_pinhole": (ctypes.c_int, [vp, vp, vp, f32, i32, i32, ctypes.POINTER(_Camera)]),
         "rt_camera_reference": (ctypes.c_int, [vp, ctypes.POINTER(_Camera)]),
+        "rt_accel_build": (ctypes.c_int, [ctypes.POINTER(_Scene), vp]),
+        "rt_accel_build_device": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, vp]),
+        "rt_accel_kept": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp, i32, vp]),
+        "rt_cast_rays_accel": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp, vp,
+                                              vp]),
+        "rt_occlude_rays_accel": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp,
+                                                 vp]),
+        "rt_cast_camera_accel": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.POINTER(_Scene),
+                                                vp, i32, i32, i32, vp, vp]),
+        "rt_cast_rays_accel_device": (ctypes.c_int, [vp, vp, ctypes.c_int64,
+                                                     ctypes.POINTER(_Scene), vp, vp, vp, vp]),
+        "rt_occlude_rays_accel_device": (ctypes.c_int, [vp, vp, ctypes.c_int64,
+                                                        ctypes.POINTER(_Scene), vp, vp, vp]),
+        "rt_cast_camera_accel_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera),
+                                                       ctypes.POINTER(_Scene), vp, i32, i32, i32,
+                                                       vp, vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -808,6 +833,75 @@ def cast_camera(camera: Camera, scene: Scene, width: int, height: int,
     return (out, tri) if triangles else out
 
 
+def _accel(accel: np.ndarray, scene: Scene) -> np.ndarray:
+    accel = np.ascontiguousarray(accel)
+    if accel.dtype != CUBE_BOUND_DTYPE or accel.shape != (scene.num_cubes,):
+        raise ValueError(f"accel must be build_accel(scene)'s array, got {accel.dtype} "
+                         f"{accel.shape}")
+    return accel
+
+
+def build_accel(scene: Scene) -> np.ndarray:
+    """rt_accel_build: one CUBE_BOUND_DTYPE record per cube of `scene`, for
+    the *_accel ray queries.  Build once per scene; rebuild after any change of
+    the cube vertices (a stale record gives wrong results).  On the host."""
+    out = np.zeros(scene.num_cubes, CUBE_BOUND_DTYPE)
+    sc = scene.as_c()
+    _check(library().rt_accel_build(ctypes.byref(sc), _ptr(out)), "rt_accel_build")
+    return out
+
+
+def accel_kept(rays: np.ndarray, scene: Scene, accel: np.ndarray,
+               segment: bool = False) -> np.ndarray:
+    """rt_accel_kept: per ray the int32 number of cubes other than its `skip`
+    that the keep test keeps (segment=False: cast_rays_accel's test, True:
+    occlude_rays_accel's).  On the host."""
+    rays, accel = _rays(rays), _accel(accel, scene)
+    out = np.empty(rays.shape, np.int32)
+    sc = scene.as_c()
+    _check(library().rt_accel_kept(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
+                                   int(bool(segment)), _ptr(out)), "rt_accel_kept")
+    return out
+
+
+def cast_rays_accel(rays: np.ndarray, scene: Scene, accel: np.ndarray, triangles: bool = False):
+    """rt_cast_rays_accel: cast_rays' result word for word, with the cubes that
+    `accel` (build_accel(scene)) proves missed left out per ray.  On the host."""
+    rays, accel = _rays(rays), _accel(accel, scene)
+    out = np.empty(rays.shape, HIT_DTYPE)
+    tri = np.empty(rays.shape, np.int32) if triangles else None
+    sc = scene.as_c()
+    _check(library().rt_cast_rays_accel(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
+                                        _ptr(out), _ptr(tri)), "rt_cast_rays_accel")
+    return (out, tri) if triangles else out
+
+
+def occlude_rays_accel(rays: np.ndarray, scene: Scene, accel: np.ndarray) -> np.ndarray:
+    """rt_occlude_rays_accel: occlude_rays' result word for word, culled by
+    `accel`.  On the host."""
+    rays, accel = _rays(rays), _accel(accel, scene)
+    out = np.empty(rays.shape, np.uint8)
+    sc = scene.as_c()
+    _check(library().rt_occlude_rays_accel(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
+                                           _ptr(out)), "rt_occlude_rays_accel")
+    return out
+
+
+def cast_camera_accel(camera: Camera, scene: Scene, accel: np.ndarray, width: int, height: int,
+                      rows: Optional[Tuple[int, int]] = None, triangles: bool = False):
+    """rt_cast_camera_accel: cast_camera's frame word for word, culled by
+    `accel`.  On the host."""
+    accel = _accel(accel, scene)
+    rb, re = rows if rows is not None else (0, height)
+    shape = (max(re - rb, 0), max(width, 0))
+    out = np.empty(shape, HIT_DTYPE)
+    tri = np.empty(shape, np.int32) if triangles else None
+    c, sc = camera.as_c(), scene.as_c()
+    _check(library().rt_cast_camera_accel(ctypes.byref(c), ctypes.byref(sc), _ptr(accel), width,
+                                          rb, re, _ptr(out), _ptr(tri)), "rt_cast_camera_accel")
+    return (out, tri) if triangles else out
+
+
 def _device_scene(device_scene: dict) -> _Scene:
     """rt_scene of device addresses, lights included (hit post-passes)."""
     g = device_scene.get
@@ -1061,6 +1155,43 @@ class RayTracer:
                                                rows[0], rows[1], hits_ptr or None,
                                                triangles_ptr or None, stream or None),
                "rt_cast_camera_device")
+
+    def build_accel_device(self, device_scene: dict, out_ptr: int, stream: int = 0) -> None:
+        """rt_accel_build_device: one rt_cube_bound (320 bytes) per cube of
+        `device_scene` at the device address `out_ptr` (16-byte aligned).
+        Asynchronous on `stream`."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_accel_build_device(self._ctx, ctypes.byref(sc), out_ptr or None,
+                                               stream or None), "rt_accel_build_device")
+
+    def cast_rays_accel_device(self, rays_ptr: int, n: int, device_scene: dict, accel_ptr: int,
+                               hits_ptr: int, triangles_ptr: int = 0, stream: int = 0) -> None:
+        """rt_cast_rays_accel_device: cast_rays_device culled by the records
+        at `accel_ptr` (build_accel_device's, of this scene).  Asynchronous."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_cast_rays_accel_device(
+            self._ctx, rays_ptr or None, n, ctypes.byref(sc), accel_ptr or None, hits_ptr or None,
+            triangles_ptr or None, stream or None), "rt_cast_rays_accel_device")
+
+    def occlude_rays_accel_device(self, rays_ptr: int, n: int, device_scene: dict, accel_ptr: int,
+                                  out_ptr: int, stream: int = 0) -> None:
+        """rt_occlude_rays_accel_device: occlude_rays_device culled by the
+        records at `accel_ptr`.  Asynchronous on `stream`."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_occlude_rays_accel_device(
+            self._ctx, rays_ptr or None, n, ctypes.byref(sc), accel_ptr or None, out_ptr or None,
+            stream or None), "rt_occlude_rays_accel_device")
+
+    def cast_camera_accel_device(self, camera: Camera, device_scene: dict, accel_ptr: int,
+                                 width: int, rows: Tuple[int, int], hits_ptr: int,
+                                 triangles_ptr: int = 0, stream: int = 0) -> None:
+        """rt_cast_camera_accel_device: cast_camera_device culled by the
+        records at `accel_ptr`.  Asynchronous on `stream`."""
+        c, sc = camera.as_c(), _device_scene(device_scene)
+        _check(library().rt_cast_camera_accel_device(
+            self._ctx, ctypes.byref(c), ctypes.byref(sc), accel_ptr or None, width, rows[0],
+            rows[1], hits_ptr or None, triangles_ptr or None, stream or None),
+            "rt_cast_camera_accel_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,

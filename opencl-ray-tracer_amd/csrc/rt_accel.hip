@@ -1,0 +1,279 @@
+// rt_accel.hip -- rt_accel_build_device and rt_cast_rays_accel_device /
+// rt_occlude_rays_accel_device / rt_cast_camera_accel_device: the culled ray
+// queries on the device.  The kernels of rt_rays.hip with
+// one more condition in front of a cube's twelve triangle tests: the keep test
+// of include/rt_accel_impl.h on the cube's prebuilt record, the text the host
+// functions compile.
+//
+// The walks stay wave-uniform: cube, triangle and sphere are loop counters, so
+// the scene and now the record (320 bytes per cube) come through scalar loads,
+// once per wave.  A lane that does not keep a cube does not test it: the
+// ballot skips the cube where no lane of the wave keeps it, so coherent rays
+// profit most.  Spheres keep their unculled loop.
+//
+// The ray prologues and the launch are rt_rays.hip's, restated here so that
+// that file and its kernels stay as they are.
+#include "rt_light_device.inc"
+#include "rt_accel_impl.h"
+
+namespace {
+
+enum { kFromRays = 0, kFromCamera = 1 };
+
+// Ray i of a ray array: two 16-byte loads.
+__device__ __forceinline__ rt_light::Ray load_ray(const rt_ray* __restrict__ rays, int64_t i,
+                                                  const rt_scene& s, int32_t& skip) {
+    const float4* r = reinterpret_cast<const float4*>(rays) + 2 * i;
+    const float4 a = r[0], b = r[1];
+    skip = rt_light::ray_skip(s, __float_as_int(a.w));
+    return rt_light::Ray{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
+}
+
+// Ray i of a camera's band of n = rows * width pixels.
+__device__ __forceinline__ rt_light::Ray camera_ray_at(const rt_camera& cam, int64_t i, int64_t n,
+                                                       int32_t width, int32_t row_begin) {
+    int32_t x, r;
+    if (n <= (int64_t)UINT32_MAX) {  // (uniform) the 32-bit division is several times cheaper
+        const uint32_t q = (uint32_t)i / (uint32_t)width;
+        r = (int32_t)q;
+        x = (int32_t)((uint32_t)i - q * (uint32_t)width);
+    } else {
+        const int64_t q = i / width;
+        r = (int32_t)q;
+        x = (int32_t)(i - q * width);
+    }
+    return rt_light::camera_ray(cam, (float)x, (float)(row_begin + r));  // exact: both <= 2^24
+}
+
+// wave_bounce_walk of rt_light_device.inc with the keep test: a lane tests
+// cube j iff it casts, j is not its own and its ray keeps the cube.
+__device__ __forceinline__ rt_light::Bounce wave_bounce_walk_culled(
+    const rt_scene& s, const rt_cube_bound* __restrict__ accel, rt_light::Vec3 p,
+    rt_light::Vec3 R, int32_t own, bool casts) {
+    rt_light::Bounce b{rt_light::kFar, -1, -1};
+    const double pd[3] = {p.x, p.y, p.z};
+    const double Rd[3] = {R.x, R.y, R.z};
+    float sf;
+    for (int32_t j = 0; j < s.num_cubes; ++j) {
+        const bool mine = casts && own != j && rt_light::cube_kept(pd, Rd, accel[j], false);
+        if (__ballot(mine) == 0) continue;
+        const float* v = s.cube_vertices + 144 * (int64_t)j;
+        for (int tri = 0; tri < 12; ++tri)
+            if (mine && rt_light::bounce_tri(pd, Rd, v + 12 * tri, &sf) && sf < b.best)
+                b = rt_light::Bounce{sf, j, tri};
+    }
+    // (sphere sp is object num_cubes + sp; own < 2^31 so the sum fits)
+    for (int32_t sp = 0; sp < s.num_spheres; ++sp)
+        if (casts && own - s.num_cubes != sp &&
+            rt_light::bounce_sphere(p, R, s.sphere_origins + 4 * (int64_t)sp, s.sphere_radius[sp],
+                                    &sf) &&
+            sf < b.best)
+            b = rt_light::Bounce{sf, s.num_cubes + sp, -1};
+    return b;
+}
+
+// occluder_walk of rt_light_device.inc with the keep test; its early-outs stay.
+__device__ __forceinline__ bool occluder_walk_culled(const rt_scene& s,
+                                                     const rt_cube_bound* __restrict__ accel,
+                                                     const double* pd, rt_light::Vec3 p,
+                                                     rt_light::Vec3 L, int32_t own, bool pending) {
+    if (__ballot(pending) == 0) return pending;
+    const double Ld[3] = {L.x, L.y, L.z};
+    for (int32_t j = 0; j < s.num_cubes; ++j) {
+        const bool mine = pending && own != j && rt_light::cube_kept(pd, Ld, accel[j], true);
+        if (__ballot(mine) == 0) continue;
+        const float* v = s.cube_vertices + 144 * (int64_t)j;
+        for (int tri = 0; tri < 12; ++tri) {
+            if (mine && pending && rt_light::occluded_by_tri(pd, Ld, v + 12 * tri))
+                pending = false;
+            if (__ballot(mine && pending) == 0) break;
+        }
+        if (__ballot(pending) == 0) break;
+    }
+    if (__ballot(pending) != 0) {
+        for (int32_t sp = 0; sp < s.num_spheres; ++sp) {
+            if (pending && own - s.num_cubes != sp &&
+                rt_light::occluded_by_sphere(p, L, s.sphere_origins + 4 * (int64_t)sp,
+                                             s.sphere_radius[sp]))
+                pending = false;
+            if (__ballot(pending) == 0) break;
+        }
+    }
+    return pending;
+}
+
+// cast_kernel of rt_rays.hip over the culled walk.
+template <int kSource>
+__global__ void __launch_bounds__(256)
+cast_accel_kernel(const rt_ray* __restrict__ rays, rt_hit* __restrict__ out_hits,
+                  int32_t* __restrict__ out_triangle, const rt_cube_bound* __restrict__ accel,
+                  int64_t n, int32_t width, int32_t row_begin, rt_camera cam, rt_scene s) {
+    const int64_t i = pixel_index();
+    const bool live = i < n;
+    rt_light::Ray r{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    int32_t skip = -1;
+    if constexpr (kSource == kFromRays) {
+        if (live) r = load_ray(rays, i, s, skip);
+    } else {
+        r = camera_ray_at(cam, i, n, width, row_begin);
+        // the ray is six opaque registers from here on, as in rt_rays.hip
+        asm("" : "+v"(r.o.x), "+v"(r.o.y), "+v"(r.o.z), "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z));
+    }
+    const rt_light::Bounce b = wave_bounce_walk_culled(s, accel, r.o, r.d, skip, live);
+    if (live) {
+        reinterpret_cast<int2*>(out_hits)[i] = make_int2(__float_as_int(b.best), b.obj2);
+        if (out_triangle) out_triangle[i] = b.tri2;
+    }
+}
+
+// occlude_kernel of rt_rays.hip over the culled walk.
+__global__ void __launch_bounds__(256)
+occlude_accel_kernel(const rt_ray* __restrict__ rays, uint8_t* __restrict__ out,
+                     const rt_cube_bound* __restrict__ accel, int64_t n, rt_scene s) {
+    const int64_t i = pixel_index();
+    const bool live = i < n;
+    rt_light::Ray r{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
+    int32_t skip = -1;
+    if (live) r = load_ray(rays, i, s, skip);
+    const double pd[3] = {r.o.x, r.o.y, r.o.z};
+    const bool clear = occluder_walk_culled(s, accel, pd, r.o, r.d, skip, live);
+    if (live) out[i] = clear ? 0 : 1;
+}
+
+template <typename T, typename F>
+__device__ __forceinline__ T wave_reduce(T v, F f) {
+    for (int m = 32; m >= 1; m >>= 1) v = f(v, __shfl_xor(v, m));
+    return v;
+}
+
+// rt_light::cube_bound for a wave: one wave per cube, four per workgroup.
+// Lanes 0..35 hold one vertex each (one coalesced 576-byte read; the lanes
+// above repeat vertex 0, which changes no minimum or maximum); lane 3k holds
+// triangle k after two shuffles and computes its edges and normal by the
+// host's text; min, max and the largest edge are butterflies, whose result
+// does not depend on the order.  Lane 0 stores the 32-byte head as two
+// 16-byte stores, lane 3k its normal.
+__global__ void __launch_bounds__(256)
+accel_build_kernel(const float* __restrict__ cube_vertices, rt_cube_bound* __restrict__ out,
+                   int32_t num_cubes) {
+    const int32_t lane = threadIdx.x & 63;
+    const int32_t j = (int32_t)blockIdx.x * 4 + (int32_t)(threadIdx.x >> 6);  // (< 2^31: the grid)
+    if (j >= num_cubes) return;  // (wave-uniform)
+    const float4 v = reinterpret_cast<const float4*>(cube_vertices)[36 * (int64_t)j +
+                                                                    (lane < 36 ? lane : 0)];
+    const bool bad = !(rt_light::finite_f(v.x) && rt_light::finite_f(v.y) && rt_light::finite_f(v.z));
+    const bool finite = __ballot(bad) == 0;
+    // triangle k in lane 3k: v1 and v2 from the next two lanes
+    float tri[12] = {v.x, v.y, v.z, 0.0f, __shfl_down(v.x, 1), __shfl_down(v.y, 1),
+                     __shfl_down(v.z, 1), 0.0f, __shfl_down(v.x, 2), __shfl_down(v.y, 2),
+                     __shfl_down(v.z, 2), 0.0f};
+    const bool owns = lane < 36 && lane % 3 == 0;
+    double nrm[3] = {0.0, 0.0, 0.0}, emax = 0.0;
+    if (owns && finite) {
+        const double l1 = rt_light::edge_len2(tri, tri + 4), l2 = rt_light::edge_len2(tri, tri + 8);
+        emax = l1 > l2 ? l1 : l2;
+        rt_light::tri_normal(tri, nrm);
+    }
+    const auto fmin_ = [](float a, float b) { return b < a ? b : a; };
+    const auto fmax_ = [](float a, float b) { return b > a ? b : a; };
+    const float inf = __builtin_huge_valf();
+    float4 lo, hi;
+    if (finite) {
+        // (+ 0.0f: a zero bound is +0 whichever of -0 and +0 the order met first)
+        lo = make_float4(wave_reduce(v.x, fmin_) + 0.0f, wave_reduce(v.y, fmin_) + 0.0f,
+                         wave_reduce(v.z, fmin_) + 0.0f, 0.0f);
+        hi = make_float4(wave_reduce(v.x, fmax_) + 0.0f, wave_reduce(v.y, fmax_) + 0.0f,
+                         wave_reduce(v.z, fmax_) + 0.0f, 0.0f);
+        emax = wave_reduce(emax, [](double a, double b) { return b > a ? b : a; });
+        lo.w = rt_light::float_up(emax);
+    } else {
+        lo = make_float4(-inf, -inf, -inf, inf);
+        hi = make_float4(inf, inf, inf, 0.0f);
+    }
+    rt_cube_bound* o = out + j;
+    if (lane == 0) {
+        reinterpret_cast<float4*>(o)[0] = lo;
+        reinterpret_cast<float4*>(o)[1] = hi;
+    }
+    if (owns) {
+        double* nk = o->normal[lane / 3];
+        nk[0] = nrm[0];
+        nk[1] = nrm[1];
+        nk[2] = nrm[2];
+    }
+}
+
+// What every ray entry point does after its checks (launch_rays of rt_rays.hip).
+template <typename Enqueue>
+int launch_rays(rt_ctx* ctx, int64_t n, int64_t per_block, void* stream, Enqueue enqueue) {
+    if (n == 0) return RT_OK;
+    const int64_t blocks = (n + per_block - 1) / per_block;  // (<= INT32_MAX: the checks)
+    if (hipSetDevice(rt_internal::ctx_device(ctx)) != hipSuccess) return RT_ERR_HIP;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : rt_internal::ctx_stream(ctx);
+    if (!st) return RT_ERR_HIP;
+    enqueue(dim3((unsigned)blocks), st);
+    return hipGetLastError() == hipSuccess ? RT_OK : RT_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_accel_build_device(rt_ctx* ctx, const rt_scene* device_scene, rt_cube_bound* device_out,
+                          void* stream) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    const int rc = rt_light::check_accel_build(device_scene, device_out);
+    if (rc) return rc;
+    return launch_rays(ctx, device_scene->num_cubes, 4, stream, [&](dim3 grid, hipStream_t st) {
+        accel_build_kernel<<<grid, dim3(256), 0, st>>>(device_scene->cube_vertices, device_out,
+                                                       device_scene->num_cubes);
+    });
+}
+
+int rt_cast_rays_accel_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                              const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                              rt_hit* device_out_hits, int32_t* device_out_triangle,
+                              void* stream) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = rt_light::check_rays(device_rays, n, device_scene, device_out_hits, sizeof(rt_hit),
+                                  device_out_triangle);
+    if (!rc) rc = rt_light::check_accel(device_scene, device_accel);
+    if (rc) return rc;
+    return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
+        cast_accel_kernel<kFromRays><<<grid, dim3(256), 0, st>>>(
+            device_rays, device_out_hits, device_out_triangle, device_accel, n, 1, 0, rt_camera{},
+            *device_scene);
+    });
+}
+
+int rt_occlude_rays_accel_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                                 const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                                 uint8_t* device_out_occluded, void* stream) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = rt_light::check_rays(device_rays, n, device_scene, device_out_occluded, 1, nullptr);
+    if (!rc) rc = rt_light::check_accel(device_scene, device_accel);
+    if (rc) return rc;
+    return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
+        occlude_accel_kernel<<<grid, dim3(256), 0, st>>>(device_rays, device_out_occluded,
+                                                         device_accel, n, *device_scene);
+    });
+}
+
+int rt_cast_camera_accel_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene* device_scene,
+                                const rt_cube_bound* device_accel, int32_t width,
+                                int32_t row_begin, int32_t row_end, rt_hit* device_out_hits,
+                                int32_t* device_out_triangle, void* stream) {
+    if (!ctx) return RT_ERR_INVALID_ARG;
+    int rc = rt_light::check_camera(camera, device_scene, true, width, row_begin, row_end,
+                                    device_out_hits, sizeof(rt_hit), device_out_triangle);
+    if (!rc) rc = rt_light::check_accel(device_scene, device_accel);
+    if (rc) return rc;
+    const int64_t n = (int64_t)(row_end - row_begin) * width;
+    return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
+        cast_accel_kernel<kFromCamera><<<grid, dim3(256), 0, st>>>(
+            nullptr, device_out_hits, device_out_triangle, device_accel, n, width, row_begin,
+            *camera, *device_scene);
+    });
+}
+
+}  // extern "C"

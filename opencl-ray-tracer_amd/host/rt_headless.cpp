@@ -11,7 +11,7 @@
 //               [--synthetic N M k] [--rows A B] [--ppm out.ppm] [--repeat R]
 //               [--bands B] [--devices D] [--device-scene]
 //               [--format i32x4|rgba8|hit] [--throughput F [--inflight S]]
-//               [--known-answer] [--pick X,Y] [--camera EX,EY,EZ,TX,TY,TZ,FOVY]
+//               [--known-answer] [--pick X,Y] [--camera EX,EY,EZ,TX,TY,TZ,FOVY [--accel]]
 //
 // --camera (one band, no --device-scene / --throughput): a perspective view
 // instead of the reference's orthographic one.  A pinhole at (EX, EY, EZ)
@@ -22,6 +22,9 @@
 // --format i32x4 / rgba8, shaded on the host with rt_shade_hits; hash, --pick
 // and --ppm then see that frame as they see a render's.  These are the ray
 // queries' forward-only tests (rt_hip.h), not the render's `collide`.
+// --accel (with --camera): the cube records are built on the device
+// (rt_accel_build_device) and the culled cast rt_cast_camera_accel_device
+// casts the frame; the frame is the same, byte for byte.
 //
 // --known-answer (reference scene 1, 2 or 3, 640x480, int32x4, the whole
 // frame, seed 1): checks the frame against the reference's own CPU frame as
@@ -169,12 +172,15 @@ int render_device_scene(Band& band, int width, int height, int row_begin, int ro
 
 // --camera: the scene uploaded, one rt_cast_camera_device launch over the
 // band's rows, the hit frame read back and shaded into `pixels` (`fmt`).
+// `accel`: the cube records built on the device first (rt_accel_build_device)
+// and the culled cast (rt_cast_camera_accel_device): the same frame.
 int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int width,
-                  int32_t fmt, std::vector<int32_t>& pixels) {
+                  int32_t fmt, bool accel, std::vector<int32_t>& pixels) {
     const size_t px = (size_t)width * (size_t)(band.row_end - band.row_begin);
     const size_t ns = (size_t)scene.num_spheres, nc = (size_t)scene.num_cubes;
     float *so = nullptr, *sr = nullptr, *sc = nullptr, *cv = nullptr, *cc = nullptr;
     rt_hit* out = nullptr;
+    rt_cube_bound* bounds = nullptr;
     std::vector<rt_hit> hits(px);
     auto upload = [](float** dev, const float* host, size_t floats) {
         if (floats == 0) return true;  // (an empty array stays NULL)
@@ -185,10 +191,20 @@ int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int w
     if (upload(&so, scene.sphere_origins, 4 * ns) && upload(&sr, scene.sphere_radius, ns) &&
         upload(&sc, scene.sphere_colours, 4 * ns) && upload(&cv, scene.cube_vertices, 144 * nc) &&
         upload(&cc, scene.cube_colours, 4 * nc) &&
+        (!accel || nc == 0 || hipMalloc(&bounds, nc * sizeof(rt_cube_bound)) == hipSuccess) &&
         hipMalloc(&out, px * sizeof(rt_hit)) == hipSuccess) {
         const rt_scene dev{so, sr, sc, scene.num_spheres, cv, cc, scene.num_cubes, nullptr, 0};
-        int rc = rt_cast_camera_device(band.ctx, &cam, &dev, width, band.row_begin, band.row_end,
+        int rc;
+        if (accel) {
+            rc = rt_accel_build_device(band.ctx, &dev, bounds, nullptr);
+            if (rc == RT_OK)
+                rc = rt_cast_camera_accel_device(band.ctx, &cam, &dev, bounds, width,
+                                                 band.row_begin, band.row_end, out, nullptr,
+                                                 nullptr);
+        } else {
+            rc = rt_cast_camera_device(band.ctx, &cam, &dev, width, band.row_begin, band.row_end,
                                        out, nullptr, nullptr);
+        }
         if (rc == RT_OK && (hipDeviceSynchronize() != hipSuccess ||
                             hipMemcpy(hits.data(), out, px * sizeof(rt_hit),
                                       hipMemcpyDeviceToHost) != hipSuccess))
@@ -206,7 +222,8 @@ int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int w
     } else {
         std::fprintf(stderr, "scene upload failed\n");
     }
-    for (void* p : {(void*)so, (void*)sr, (void*)sc, (void*)cv, (void*)cc, (void*)out})
+    for (void* p : {(void*)so, (void*)sr, (void*)sc, (void*)cv, (void*)cc, (void*)out,
+                    (void*)bounds})
         if (p) (void)hipFree(p);
     return status;
 }
@@ -327,7 +344,7 @@ int main(int argc, char** argv) {
     int32_t fmt = RT_FORMAT_I32X4;
     bool known_answer = false;
     int pick_x = -1, pick_y = -1;
-    bool camera = false;
+    bool camera = false, accel = false;
     float cam_v[7] = {};
     std::string ppm;
     for (int i = 1; i < argc; ++i) {
@@ -374,6 +391,8 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (a == "--accel")
+            accel = true;
         else if (a == "--camera") {
             camera = std::sscanf(next(), "%f,%f,%f,%f,%f,%f,%f", &cam_v[0], &cam_v[1], &cam_v[2],
                                  &cam_v[3], &cam_v[4], &cam_v[5], &cam_v[6]) == 7;
@@ -407,6 +426,10 @@ int main(int argc, char** argv) {
     }
     if (device_scene && (syn_n < 0 || n_bands != 1)) {
         std::fprintf(stderr, "--device-scene needs --synthetic and one band\n");
+        return 2;
+    }
+    if (accel && !camera) {
+        std::fprintf(stderr, "--accel needs --camera\n");
         return 2;
     }
     rt_camera cam{};
@@ -490,7 +513,7 @@ int main(int argc, char** argv) {
     int status = 0;
     if (camera) {
         std::printf("HIP Ray Tracer Begin\n");
-        status = render_camera(bands[0], scene, cam, width, fmt, pixels);
+        status = render_camera(bands[0], scene, cam, width, fmt, accel, pixels);
         if (status == 0)
             std::printf("camera eye (%g, %g, %g) target (%g, %g, %g) fov %g: one ray per pixel\n",
                         (double)cam_v[0], (double)cam_v[1], (double)cam_v[2], (double)cam_v[3],
