@@ -113,6 +113,14 @@ RT_LIGHT_FN rt_cube_bound cube_bound(const float* verts) {
 
 RT_LIGHT_FN double abs_d(double x) { return fabs(x); }
 
+// How the loop over the record's twelve normals in cube_kept is compiled:
+// nothing (the compiler's choice: unrolled whole, the record in flight at once)
+// or a loop pragma of the including translation unit, which changes the
+// instruction schedule and nothing that is computed.
+#ifndef RT_ACCEL_NORMALS_LOOP
+#define RT_ACCEL_NORMALS_LOOP
+#endif
+
 // Is it proven that the parameter range [0, inf) (segment: [0, 1]) of the ray
 // misses the record's box grown by `delta` on every side?  The slab test, one
 // reciprocal per axis; a comparison that meets a NaN proves nothing.
@@ -178,6 +186,7 @@ RT_LIGHT_FN bool cube_kept(const double* o, const double* d, const rt_cube_bound
     const double graze_below = 4.0 * eps;
     double g = kAccelInf, asum = 0.0;
     bool graze = false;
+    RT_ACCEL_NORMALS_LOOP
     for (int k = 0; k < 12; ++k) {
         const double q = (d[0] * b.normal[k][0] + d[1] * b.normal[k][1]) + d[2] * b.normal[k][2];
         const double a = abs_d(q);
@@ -235,6 +244,18 @@ RT_LIGHT_FN bool light_occluded_culled(const rt_scene& s, const rt_cube_bound* a
     }
     return false;
 }
+
+// rt_light_impl.h's Walks over the two culled walks: what the pixel functions
+// of the *_accel light pass take.
+struct CulledWalks {
+    const rt_cube_bound* accel;
+    RT_LIGHT_FN bool occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L) const {
+        return light_occluded_culled(s, accel, obj, p, L);
+    }
+    RT_LIGHT_FN Bounce bounce(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R) const {
+        return bounce_walk_culled(s, accel, obj, p, R);
+    }
+};
 
 }  // namespace rt_light
 

@@ -741,6 +741,56 @@ int rt_cast_camera_accel_device(rt_ctx* ctx, const rt_camera* camera, const rt_s
                                 int32_t row_begin, int32_t row_end, rt_hit* device_out_hits,
                                 int32_t* device_out_triangle, void* stream);
 
+/* ---- the light pass over the same records ---------------- */
+/* The walks of the deferred light pass, culled by the records above: each call
+ * is the call of the same name without `_accel`, with `accel` directly after
+ * the scene, and returns that call's output word for word on every input.  A
+ * pixel tests cube j only where j is not its own and the keep test keeps j for
+ * its shadow segment (the occlusion test's form) or its bounce (the cast's).
+ * Order, tie rule, early-outs, the sphere loops, the level loop and the
+ * backward blend are the unculled calls'.
+ *
+ * rt_shadow_hits_accel*: rt_shadow_hits*' uint32 mask per pixel.
+ * rt_bounce_hits_accel*: rt_bounce_hits*' hit frame of bounce 1 ..
+ * RT_MAX_BOUNCES (bounce 1 is rt_reflect_hits*' frame).
+ * rt_light_hits_mirrored_accel*: rt_light_hits_mirrored*' lit frame; with
+ * max_bounces 0 and shadows 1 that is rt_light_hits_shadowed*' frame, with
+ * max_bounces 1 and one reflectivity everywhere rt_light_hits_reflected*' and
+ * rt_light_hits_shadowed_reflected*', so the three calls cover every lit frame.
+ *
+ * The unculled call's contract, and RT_ERR_INVALID_ARG for a NULL or
+ * misaligned (16 bytes) accel with num_cubes > 0; with num_cubes == 0 accel
+ * may be NULL.  A stale or foreign accel is not detectable.  Device calls:
+ * checked before any HIP call; asynchronous on `stream`; one launch, no
+ * workspace. */
+int rt_shadow_hits_accel(const rt_hit* hits, const rt_scene* scene, const rt_cube_bound* accel,
+                         const float ray_dir[4], int32_t width, int32_t row_begin,
+                         int32_t row_end, uint32_t* out);
+int rt_shadow_hits_accel_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                                const float ray_dir[4], int32_t width, int32_t row_begin,
+                                int32_t row_end, uint32_t* device_out, void* stream);
+int rt_bounce_hits_accel(const rt_hit* hits, const rt_scene* scene, const rt_cube_bound* accel,
+                         const float ray_dir[4], int32_t width, int32_t row_begin,
+                         int32_t row_end, int32_t bounce, rt_hit* out);
+int rt_bounce_hits_accel_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                                const float ray_dir[4], int32_t width, int32_t row_begin,
+                                int32_t row_end, int32_t bounce, rt_hit* device_out,
+                                void* stream);
+int rt_light_hits_mirrored_accel(const rt_hit* hits, const rt_scene* scene,
+                                 const rt_cube_bound* accel, const float ray_dir[4],
+                                 int32_t width, int32_t row_begin, int32_t row_end,
+                                 const float* reflectivity, int32_t max_bounces, int32_t shadows,
+                                 int32_t out_format, void* out);
+int rt_light_hits_mirrored_accel_device(rt_ctx* ctx, const rt_hit* device_hits,
+                                        const rt_scene* device_scene,
+                                        const rt_cube_bound* device_accel, const float ray_dir[4],
+                                        int32_t width, int32_t row_begin, int32_t row_end,
+                                        const float* device_reflectivity, int32_t max_bounces,
+                                        int32_t shadows, int32_t out_format, void* device_out,
+                                        void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

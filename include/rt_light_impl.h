@@ -263,29 +263,39 @@ RT_LIGHT_FN bool light_occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L) 
     return false;
 }
 
+// The two walks of a pixel function, as one value: light_occluded and
+// bounce_walk (defined behind bounce_walk below).  The pixel functions that walk
+// are templates over it with this pair as the default; the *_accel calls pass
+// rt_accel_impl.h's culled pair, so each level loop has one text.
+struct Walks;
+
 // Bit i: light i faces the pixel (c > 0) and is occluded.  At most 32 lights
 // (the callers refuse more); n is the faced normal of a hit pixel.
-RT_LIGHT_FN uint32_t shadow_mask(const rt_scene& s, int32_t obj, Vec3 n, Vec3 p) {
+template <typename W = Walks>
+RT_LIGHT_FN uint32_t shadow_mask(const rt_scene& s, int32_t obj, Vec3 n, Vec3 p,
+                                 const W& w = W()) {
     uint32_t mask = 0;
     for (int32_t i = 0; i < s.num_lights && i < 32; ++i) {
         const float* l = s.lights + 4 * static_cast<int64_t>(i);
         const Vec3 L{l[0] - p.x, l[1] - p.y, l[2] - p.z};
         const float ll = sqrtf((L.x * L.x + L.y * L.y) + L.z * L.z);
         const float c = ((n.x * L.x + n.y * L.y) + n.z * L.z) / ll;
-        if (c > 0.0f && light_occluded(s, obj, p, L)) mask |= 1u << i;
+        if (c > 0.0f && w.occluded(s, obj, p, L)) mask |= 1u << i;
     }
     return mask;
 }
 
 // light_factor with the occluded lights left out of the sum.
-RT_LIGHT_FN float shadowed_factor(const rt_scene& s, int32_t obj, Vec3 n, Vec3 p) {
+template <typename W = Walks>
+RT_LIGHT_FN float shadowed_factor(const rt_scene& s, int32_t obj, Vec3 n, Vec3 p,
+                                  const W& w = W()) {
     float k = 0.0f;
     for (int32_t i = 0; i < s.num_lights; ++i) {
         const float* l = s.lights + 4 * static_cast<int64_t>(i);
         const Vec3 L{l[0] - p.x, l[1] - p.y, l[2] - p.z};
         const float ll = sqrtf((L.x * L.x + L.y * L.y) + L.z * L.z);
         const float c = ((n.x * L.x + n.y * L.y) + n.z * L.z) / ll;
-        if (c > 0.0f && !light_occluded(s, obj, p, L)) k = k + c;
+        if (c > 0.0f && !w.occluded(s, obj, p, L)) k = k + c;
     }
     if (k > 1.0f) k = 1.0f;
     return k;
@@ -301,24 +311,26 @@ RT_LIGHT_FN Vec3 slot_colour(const rt_scene& s, int32_t obj) {
 }
 
 // lit_pixel with shadowed_factor in place of light_factor.
+template <typename W = Walks>
 RT_LIGHT_FN void lit_pixel_shadowed(const rt_scene& s, int32_t obj, const float* verts, float ox,
-                                    float oy, Vec3 d, float t, int32_t out[4]) {
+                                    float oy, Vec3 d, float t, int32_t out[4], const W& w = W()) {
     float k = 1.0f;
     if (s.num_lights > 0 && obj >= 0) {
         const Vec3 p = hit_point(ox, oy, d, t);
         const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
-        k = shadowed_factor(s, obj, Vec3{n.nx, n.ny, n.nz}, p);
+        k = shadowed_factor(s, obj, Vec3{n.nx, n.ny, n.nz}, p, w);
     }
     shade_lit(t, k, slot_colour(s, obj), out);
 }
 
 // The mask of one pixel (0 for a miss or without lights).
+template <typename W = Walks>
 RT_LIGHT_FN uint32_t shadow_pixel(const rt_scene& s, int32_t obj, const float* verts, float ox,
-                                  float oy, Vec3 d, float t) {
+                                  float oy, Vec3 d, float t, const W& w = W()) {
     if (s.num_lights <= 0 || obj < 0) return 0;
     const Vec3 p = hit_point(ox, oy, d, t);
     const rt_surface n = surface(s, obj, verts, ox, oy, d, t, p);
-    return shadow_mask(s, obj, Vec3{n.nx, n.ny, n.nz}, p);
+    return shadow_mask(s, obj, Vec3{n.nx, n.ny, n.nz}, p, w);
 }
 
 /* ---- the mirror bounce -----------------------------------
@@ -403,6 +415,16 @@ RT_LIGHT_FN Bounce bounce_walk(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R) {
     }
     return b;
 }
+
+// The unculled pair of walks (declared in front of shadow_mask above).
+struct Walks {
+    RT_LIGHT_FN bool occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L) const {
+        return light_occluded(s, obj, p, L);
+    }
+    RT_LIGHT_FN Bounce bounce(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R) const {
+        return bounce_walk(s, obj, p, R);
+    }
+};
 
 // The unit normal at the bounce's hit point p2, turned against R.  `obj2` is
 // a colour slot of `s` and `tri2` a triangle of that cube (bounce_walk's).
@@ -604,8 +626,10 @@ RT_LIGHT_FN Vec3 chain_blend(Vec3 a, float r, Vec3 C) {
 // The geometry of bounce number `bounce` (1 .. RT_MAX_BOUNCES) of one pixel's
 // chain, followed without regard to reflectivity, lights or t.  (kFar, -1) for
 // a miss and where this bounce or an earlier one met nothing.
+template <typename W = Walks>
 RT_LIGHT_FN Bounce bounce_chain_pixel(const rt_scene& s, int32_t obj, const float* verts, float ox,
-                                      float oy, Vec3 d, float t, int32_t bounce) {
+                                      float oy, Vec3 d, float t, int32_t bounce,
+                                      const W& w = W()) {
     if (obj < 0) return Bounce{kFar, -1, -1};
     Vec3 p = hit_point(ox, oy, d, t);
     const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
@@ -613,7 +637,7 @@ RT_LIGHT_FN Bounce bounce_chain_pixel(const rt_scene& s, int32_t obj, const floa
     Vec3 D = d;
     for (int32_t j = 1;; ++j) {
         const Vec3 R = mirror_dir(n, D);
-        const Bounce b = bounce_walk(s, obj, p, R);
+        const Bounce b = w.bounce(s, obj, p, R);
         if (b.obj2 < 0 || j >= bounce) return b;
         const Vec3 p2 = bounce_point(p, R, b.best);
         n = bounce_normal(s, b.obj2, b.tri2, p2, R);
@@ -627,12 +651,14 @@ RT_LIGHT_FN Bounce bounce_chain_pixel(const rt_scene& s, int32_t obj, const floa
 // (0 .. RT_MAX_BOUNCES) bounces, blended backwards.  `reflectivity` is read at
 // the slots of levels below max_bounces only.  A miss, and t == kFar, are
 // lit_pixel's (with `shadows`, lit_pixel_shadowed's).
+template <typename W = Walks>
 RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float* verts, float ox,
                                     float oy, Vec3 d, float t, const float* reflectivity,
-                                    int32_t max_bounces, bool shadows, int32_t out[4]) {
+                                    int32_t max_bounces, bool shadows, int32_t out[4],
+                                    const W& w = W()) {
     if (obj < 0 || t == kFar) {
         if (shadows)
-            lit_pixel_shadowed(s, obj, verts, ox, oy, d, t, out);
+            lit_pixel_shadowed(s, obj, verts, ox, oy, d, t, out, w);
         else
             lit_pixel(s, obj, verts, ox, oy, d, t, out);
         return;
@@ -649,7 +675,8 @@ RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float*
     for (;; ++j) {
         float k = 1.0f;
         if (s.num_lights > 0)
-            k = shadows ? shadowed_factor(s, obj, n, p) : light_factor(n, p, s.lights, s.num_lights);
+            k = shadows ? shadowed_factor(s, obj, n, p, w)
+                        : light_factor(n, p, s.lights, s.num_lights);
         const Vec3 own = chain_colour(chain_scalar(T, j >= 1), k, slot_colour(s, obj));
         const float rj = j < max_bounces ? slot_reflectivity(reflectivity, obj) : 0.0f;
         if (!(rj != 0.0f)) {  // by depth or by a matte object: C_J = a_J
@@ -659,7 +686,7 @@ RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float*
         a[j] = own;
         r[j] = rj;
         const Vec3 R = mirror_dir(n, D);
-        const Bounce b = bounce_walk(s, obj, p, R);
+        const Bounce b = w.bounce(s, obj, p, R);
         if (b.obj2 < 0) {  // by a miss after level j: C_{j+1} = (0, 0, 0)
             ++j;
             break;

@@ -31,7 +31,7 @@ __all__ = [
     "light_hits_shadowed_reflected", "RT_MAX_BOUNCES", "bounce_hits", "light_hits_mirrored",
     "RAY_DTYPE", "Camera", "cast_rays", "occlude_rays", "camera_rays", "cast_camera",
     "CUBE_BOUND_DTYPE", "build_accel", "accel_kept", "cast_rays_accel", "occlude_rays_accel",
-    "cast_camera_accel",
+    "cast_camera_accel", "shadow_hits_accel", "bounce_hits_accel", "light_hits_mirrored_accel",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -82,6 +82,9 @@ EXPORTED_SYMBOLS = (
     "rt_accel_build", "rt_accel_build_device", "rt_accel_kept", "rt_cast_rays_accel",
     "rt_occlude_rays_accel", "rt_cast_camera_accel", "rt_cast_rays_accel_device",
     "rt_occlude_rays_accel_device", "rt_cast_camera_accel_device",
+    "rt_shadow_hits_accel", "rt_shadow_hits_accel_device", "rt_bounce_hits_accel",
+    "rt_bounce_hits_accel_device", "rt_light_hits_mirrored_accel",
+    "rt_light_hits_mirrored_accel_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -266,6 +269,19 @@ def library() -> ctypes.CDLL:
         "rt_cast_camera_accel_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera),
                                                        ctypes.POINTER(_Scene), vp, i32, i32, i32,
                                                        vp, vp, vp]),
+        "rt_shadow_hits_accel": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, vp, i32, i32, i32,
+                                                vp]),
+        "rt_shadow_hits_accel_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, vp,
+                                                       i32, i32, i32, vp, vp]),
+        "rt_bounce_hits_accel": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, vp, i32, i32, i32,
+                                                i32, vp]),
+        "rt_bounce_hits_accel_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp, vp,
+                                                       i32, i32, i32, i32, vp, vp]),
+        "rt_light_hits_mirrored_accel": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), vp, vp, i32,
+                                                        i32, i32, vp, i32, i32, i32, vp]),
+        "rt_light_hits_mirrored_accel_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp,
+                                                               vp, i32, i32, i32, vp, i32, i32,
+                                                               i32, vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -902,6 +918,65 @@ def cast_camera_accel(camera: Camera, scene: Scene, accel: np.ndarray, width: in
     return (out, tri) if triangles else out
 
 
+def shadow_hits_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray,
+                      rows: Optional[Tuple[int, int]] = None,
+                      ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_shadow_hits_accel: shadow_hits' mask word for word, the shadow
+    segments culled by `accel` (build_accel(scene)).  On the host."""
+    hits, rb, re = _hit_band(hits, rows)
+    accel = _accel(accel, scene)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(hits.shape, np.uint32)
+    sc = scene.as_c()
+    _check(library().rt_shadow_hits_accel(_ptr(hits), ctypes.byref(sc), _ptr(accel), _ptr(d),
+                                          hits.shape[1], rb, re, _ptr(out)),
+           "rt_shadow_hits_accel")
+    return out
+
+
+def bounce_hits_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray, bounce: int,
+                      rows: Optional[Tuple[int, int]] = None,
+                      ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_bounce_hits_accel: bounce_hits' frame word for word, every bounce
+    culled by `accel` (build_accel(scene)).  On the host."""
+    hits, rb, re = _hit_band(hits, rows)
+    accel = _accel(accel, scene)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    out = np.empty(hits.shape, HIT_DTYPE)
+    sc = scene.as_c()
+    _check(library().rt_bounce_hits_accel(_ptr(hits), ctypes.byref(sc), _ptr(accel), _ptr(d),
+                                          hits.shape[1], rb, re, int(bounce), _ptr(out)),
+           "rt_bounce_hits_accel")
+    return out
+
+
+def light_hits_mirrored_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray, reflectivity,
+                              max_bounces: int, fmt: str = "i32x4", shadows: bool = False,
+                              rows: Optional[Tuple[int, int]] = None,
+                              ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_light_hits_mirrored_accel: light_hits_mirrored's frame word for
+    word, the bounces and (shadows=True) the shadow segments of every level
+    culled by `accel` (build_accel(scene)).  max_bounces=0 with shadows is
+    light_hits(shadows=True)'s frame.  On the host."""
+    if fmt not in ("i32x4", "rgba8"):
+        raise ValueError("light_hits_mirrored_accel gives an i32x4 or an rgba8 frame")
+    hits, rb, re = _hit_band(hits, rows)
+    accel = _accel(accel, scene)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    refl = None
+    if reflectivity is not None:
+        refl = np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
+        if refl.size != scene.num_cubes + scene.num_spheres:
+            raise ValueError(f"reflectivity must hold one value per colour slot "
+                             f"({scene.num_cubes + scene.num_spheres}), got {refl.size}")
+    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
+    sc = scene.as_c()
+    _check(library().rt_light_hits_mirrored_accel(
+        _ptr(hits), ctypes.byref(sc), _ptr(accel), _ptr(d), hits.shape[1], rb, re, _ptr(refl),
+        int(max_bounces), int(shadows), _FORMATS[fmt], _ptr(out)), "rt_light_hits_mirrored_accel")
+    return out
+
+
 def _device_scene(device_scene: dict) -> _Scene:
     """rt_scene of device addresses, lights included (hit post-passes)."""
     g = device_scene.get
@@ -1192,6 +1267,48 @@ class RayTracer:
             self._ctx, ctypes.byref(c), ctypes.byref(sc), accel_ptr or None, width, rows[0],
             rows[1], hits_ptr or None, triangles_ptr or None, stream or None),
             "rt_cast_camera_accel_device")
+
+    def shadow_hits_accel_device(self, hits_ptr: int, device_scene: dict, accel_ptr: int,
+                                 width: int, rows: Tuple[int, int], out_ptr: int,
+                                 ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
+        """rt_shadow_hits_accel_device: shadow_hits_device culled by the
+        records at `accel_ptr` (build_accel_device's, of this scene).
+        Asynchronous on `stream`."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_shadow_hits_accel_device(
+            self._ctx, hits_ptr or None, ctypes.byref(sc), accel_ptr or None, _ptr(d), width,
+            rows[0], rows[1], out_ptr or None, stream or None), "rt_shadow_hits_accel_device")
+
+    def bounce_hits_accel_device(self, hits_ptr: int, device_scene: dict, accel_ptr: int,
+                                 width: int, rows: Tuple[int, int], out_ptr: int, bounce: int,
+                                 ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
+        """rt_bounce_hits_accel_device: bounce_hits_device culled by the
+        records at `accel_ptr`.  Asynchronous on `stream`."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_bounce_hits_accel_device(
+            self._ctx, hits_ptr or None, ctypes.byref(sc), accel_ptr or None, _ptr(d), width,
+            rows[0], rows[1], int(bounce), out_ptr or None, stream or None),
+            "rt_bounce_hits_accel_device")
+
+    def light_hits_mirrored_accel_device(self, hits_ptr: int, device_scene: dict, accel_ptr: int,
+                                         width: int, rows: Tuple[int, int], out_ptr: int,
+                                         reflectivity_ptr: int, max_bounces: int,
+                                         ray_dir: Optional[np.ndarray] = None, stream: int = 0,
+                                         fmt: str = "i32x4", shadows: bool = False) -> None:
+        """rt_light_hits_mirrored_accel_device: light_hits_mirrored_device
+        culled by the records at `accel_ptr`.  One launch, asynchronous on
+        `stream`."""
+        if fmt not in ("i32x4", "rgba8"):
+            raise ValueError("light_hits_mirrored_accel_device gives an i32x4 or an rgba8 frame")
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(library().rt_light_hits_mirrored_accel_device(
+            self._ctx, hits_ptr or None, ctypes.byref(sc), accel_ptr or None, _ptr(d), width,
+            rows[0], rows[1], reflectivity_ptr or None, int(max_bounces), int(shadows),
+            _FORMATS[fmt], out_ptr or None, stream or None),
+            "rt_light_hits_mirrored_accel_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,

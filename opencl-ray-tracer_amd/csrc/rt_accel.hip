@@ -5,16 +5,16 @@
 // of include/rt_accel_impl.h on the cube's prebuilt record, the text the host
 // functions compile.
 //
-// The walks stay wave-uniform: cube, triangle and sphere are loop counters, so
-// the scene and now the record (320 bytes per cube) come through scalar loads,
-// once per wave.  A lane that does not keep a cube does not test it: the
-// ballot skips the cube where no lane of the wave keeps it, so coherent rays
-// profit most.  Spheres keep their unculled loop.
+// The walks are rt_accel_walks.inc's, which the culled light pass shares: they
+// stay wave-uniform, so the scene and now the record (320 bytes per cube) come
+// through scalar loads, once per wave.  The ballot skips a cube where no lane
+// of the wave keeps it, so coherent rays profit most.
 //
 // The ray prologues and the launch are rt_rays.hip's, restated here so that
 // that file and its kernels stay as they are.
 #include "rt_light_device.inc"
 #include "rt_accel_impl.h"
+#include "rt_accel_walks.inc"
 
 namespace {
 
@@ -43,63 +43,6 @@ __device__ __forceinline__ rt_light::Ray camera_ray_at(const rt_camera& cam, int
         x = (int32_t)(i - q * width);
     }
     return rt_light::camera_ray(cam, (float)x, (float)(row_begin + r));  // exact: both <= 2^24
-}
-
-// wave_bounce_walk of rt_light_device.inc with the keep test: a lane tests
-// cube j iff it casts, j is not its own and its ray keeps the cube.
-__device__ __forceinline__ rt_light::Bounce wave_bounce_walk_culled(
-    const rt_scene& s, const rt_cube_bound* __restrict__ accel, rt_light::Vec3 p,
-    rt_light::Vec3 R, int32_t own, bool casts) {
-    rt_light::Bounce b{rt_light::kFar, -1, -1};
-    const double pd[3] = {p.x, p.y, p.z};
-    const double Rd[3] = {R.x, R.y, R.z};
-    float sf;
-    for (int32_t j = 0; j < s.num_cubes; ++j) {
-        const bool mine = casts && own != j && rt_light::cube_kept(pd, Rd, accel[j], false);
-        if (__ballot(mine) == 0) continue;
-        const float* v = s.cube_vertices + 144 * (int64_t)j;
-        for (int tri = 0; tri < 12; ++tri)
-            if (mine && rt_light::bounce_tri(pd, Rd, v + 12 * tri, &sf) && sf < b.best)
-                b = rt_light::Bounce{sf, j, tri};
-    }
-    // (sphere sp is object num_cubes + sp; own < 2^31 so the sum fits)
-    for (int32_t sp = 0; sp < s.num_spheres; ++sp)
-        if (casts && own - s.num_cubes != sp &&
-            rt_light::bounce_sphere(p, R, s.sphere_origins + 4 * (int64_t)sp, s.sphere_radius[sp],
-                                    &sf) &&
-            sf < b.best)
-            b = rt_light::Bounce{sf, s.num_cubes + sp, -1};
-    return b;
-}
-
-// occluder_walk of rt_light_device.inc with the keep test; its early-outs stay.
-__device__ __forceinline__ bool occluder_walk_culled(const rt_scene& s,
-                                                     const rt_cube_bound* __restrict__ accel,
-                                                     const double* pd, rt_light::Vec3 p,
-                                                     rt_light::Vec3 L, int32_t own, bool pending) {
-    if (__ballot(pending) == 0) return pending;
-    const double Ld[3] = {L.x, L.y, L.z};
-    for (int32_t j = 0; j < s.num_cubes; ++j) {
-        const bool mine = pending && own != j && rt_light::cube_kept(pd, Ld, accel[j], true);
-        if (__ballot(mine) == 0) continue;
-        const float* v = s.cube_vertices + 144 * (int64_t)j;
-        for (int tri = 0; tri < 12; ++tri) {
-            if (mine && pending && rt_light::occluded_by_tri(pd, Ld, v + 12 * tri))
-                pending = false;
-            if (__ballot(mine && pending) == 0) break;
-        }
-        if (__ballot(pending) == 0) break;
-    }
-    if (__ballot(pending) != 0) {
-        for (int32_t sp = 0; sp < s.num_spheres; ++sp) {
-            if (pending && own - s.num_cubes != sp &&
-                rt_light::occluded_by_sphere(p, L, s.sphere_origins + 4 * (int64_t)sp,
-                                             s.sphere_radius[sp]))
-                pending = false;
-            if (__ballot(pending) == 0) break;
-        }
-    }
-    return pending;
 }
 
 // cast_kernel of rt_rays.hip over the culled walk.

@@ -5,7 +5,8 @@
 // chain's rt_bounce_hits / rt_light_hits_mirrored, on the host, and
 // the argument check they share with the device entry points (the launch of
 // rt_light_device.inc, for rt_light.hip, rt_shadow.hip, rt_reflect.hip and
-// rt_shadow_reflect.hip; rt_mirror.hip's own).  One pixel loop, run(); each function is its
+// rt_shadow_reflect.hip; rt_mirror.hip's own).  One pixel loop, run() of
+// include/rt_light_run.h; each function is its
 // argument checks and the per-pixel call it hands to the loop.  Behind them the
 // ray queries, rt_cast_rays / rt_occlude_rays /
 // rt_camera_rays / rt_cast_camera: plain loops over bounce_walk, light_occluded
@@ -13,12 +14,10 @@
 // rt_rays.hip.
 // Plain C++, no HIP.  The arithmetic is include/rt_light_impl.h, the text the
 // kernel compiles too; built with -ffp-contract=off like rt_scene.cpp.
-#include <cstring>
-#include <type_traits>
-
 #include "rt_args.h"
 #include "rt_hip.h"
 #include "rt_light_impl.h"
+#include "rt_light_run.h"
 #include "rt_rays_impl.h"
 
 namespace rt_light {
@@ -65,49 +64,6 @@ int check_camera(const rt_camera* camera, const rt_scene* scene, bool with_scene
                                                                         : RT_OK;
 }
 
-namespace {
-
-// What a lit pixel function returns: the int32x4 pixel, stored in `fmt`.
-struct Lit {
-    int32_t p[4];
-};
-
-// The pixel loop of every host function: the argument check, then for every
-// pixel of the band the id range check, `pixel(s, obj, verts, ox, oy, d, t)`
-// (`obj` range-checked, `verts` = cube_verts(s, obj)) and the store of what it
-// returns: a Lit in `fmt`, anything else (rt_surface, the uint32 mask, the
-// bounce's rt_hit) as it is.  `mask`: the output holds one bit per light, so
-// at most 32.
-template <typename PixelFn>
-int run(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32_t width,
-        int32_t row_begin, int32_t row_end, bool mask, int32_t fmt, void* out, PixelFn pixel) {
-    const int rc = check(hits, scene, ray_dir, width, row_begin, row_end, out);
-    if (rc) return rc;
-    const rt_scene& s = *scene;
-    if (mask && s.num_lights > 32) return RT_ERR_UNSUPPORTED;
-    const int64_t n_slots = static_cast<int64_t>(s.num_cubes) + s.num_spheres;
-    const Vec3 d{ray_dir[0], ray_dir[1], ray_dir[2]};
-    int64_t i = 0;
-    for (int32_t y = row_begin; y < row_end; ++y) {
-        for (int32_t x = 0; x < width; ++x, ++i) {
-            const float t = hits[i].t;
-            const int32_t obj = hits[i].object;
-            if (obj < -1 || obj >= n_slots) return RT_ERR_INVALID_ARG;
-            const float ox = static_cast<float>(x), oy = static_cast<float>(y);
-            const auto v = pixel(s, obj, cube_verts(s, obj), ox, oy, d, t);
-            using Out = std::remove_const_t<decltype(v)>;
-            if constexpr (!std::is_same_v<Out, Lit>)
-                static_cast<Out*>(out)[i] = v;
-            else if (fmt == RT_FORMAT_I32X4)
-                std::memcpy(static_cast<int32_t*>(out) + 4 * i, v.p, sizeof v.p);
-            else
-                static_cast<uint32_t*>(out)[i] = pack_rgba8(v.p);
-        }
-    }
-    return RT_OK;
-}
-
-}  // namespace
 }  // namespace rt_light
 
 extern "C" {
