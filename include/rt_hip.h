@@ -791,6 +791,65 @@ int rt_light_hits_mirrored_accel_device(rt_ctx* ctx, const rt_hit* device_hits,
                                         int32_t shadows, int32_t out_format, void* device_out,
                                         void* stream);
 
+/* ---- the light pass of a camera view --------------------- */
+/* A camera's view, lit: diffuse light, hard shadows and mirror chains for the
+ * rays of an rt_camera, in one call and without a hit frame.  Pixel (x, y) of
+ * the band has the ray of rt_camera_rays*.  Level 0 of its chain is what
+ * rt_cast_camera* finds along that ray (closest hit over every object, ties to
+ * the first in cube / triangle / sphere order); a pixel whose ray meets nothing
+ * is rt_shade_hits' miss pixel (0, 0, 0, 255).  From level 0 on the pixel is
+ * rt_light_hits_mirrored*'s: per level the ramp of the summed depth T (level
+ * 0's unclamped, later ones clamped at 0) times the lighting factor (with
+ * `shadows` the occluded lights left out) times the slot's colour; the chain
+ * goes on from level j iff j < max_bounces and reflectivity[obj_j] != 0, by a
+ * bounce with obj_j alone left out, and ends at a matte object, at max_bounces
+ * or at a miss; the levels are blended backwards, a + r * (C - a).
+ *
+ * rt_light_camera*: the lit frame, RT_FORMAT_I32X4 or RT_FORMAT_RGBA8.
+ * rt_bounce_camera*: the hit frame of `bounce`: 0 is rt_cast_camera*'s frame;
+ * 1 .. RT_MAX_BOUNCES the hit of that bounce of the chain, followed without
+ * regard to reflectivity, (300000, -1) where it or an earlier level met
+ * nothing.
+ * For rt_camera_reference(d) without a -0 component in d these are
+ * rt_light_hits_mirrored* / rt_bounce_hits* on rt_cast_camera*'s frame, word
+ * for word.
+ *
+ * `accel`: NULL, every walk tests every cube; or the scene's records
+ * (rt_accel_build*), every walk is the culled one (the level-0 cast and the
+ * bounces by the cast's keep test, the shadow segments by the occlusion
+ * test's).  The output is the same word for word.
+ *
+ * Known limit, as for every bounce: a level reached from inside an object (the
+ * eye inside a sphere, whose far root the cast takes) still leaves that object
+ * out of the next bounce and of the shadow walks there.
+ *
+ * RT_ERR_INVALID_ARG: what rt_cast_camera* refuses (a NULL camera, scene or
+ * out, normalise other than 0 or 1, the band and scene checks: the band must
+ * not be empty, width >= 1 and row_begin < row_end); max_bounces
+ * outside [0, RT_MAX_BOUNCES]; bounce outside [0, RT_MAX_BOUNCES]; shadows
+ * other than 0 or 1; a format other than the two; a NULL reflectivity with
+ * max_bounces > 0 on a scene with objects (otherwise it may be NULL); on the
+ * host a reflectivity outside [0, 1] (a kernel reads such a value as 0); an
+ * `out` not aligned to 16 (int32x4), 4 (RGBA8) or 8 (rt_hit) bytes; a non-NULL
+ * accel not aligned to 16 bytes.  More than 32 lights are served.  Device
+ * calls: every array pointer is a device pointer (rt_camera and rt_scene are
+ * read on the host during the call); everything is checked before any HIP
+ * call; asynchronous on `stream` (NULL = the context's stream); one launch, no
+ * workspace, no allocation.  Host and device results are bit-identical. */
+int rt_light_camera(const rt_camera* camera, const rt_scene* scene, const rt_cube_bound* accel,
+                    int32_t width, int32_t row_begin, int32_t row_end, const float* reflectivity,
+                    int32_t max_bounces, int32_t shadows, int32_t out_format, void* out);
+int rt_light_camera_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene* device_scene,
+                           const rt_cube_bound* device_accel, int32_t width, int32_t row_begin,
+                           int32_t row_end, const float* device_reflectivity, int32_t max_bounces,
+                           int32_t shadows, int32_t out_format, void* device_out, void* stream);
+int rt_bounce_camera(const rt_camera* camera, const rt_scene* scene, const rt_cube_bound* accel,
+                     int32_t width, int32_t row_begin, int32_t row_end, int32_t bounce,
+                     rt_hit* out);
+int rt_bounce_camera_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene* device_scene,
+                            const rt_cube_bound* device_accel, int32_t width, int32_t row_begin,
+                            int32_t row_end, int32_t bounce, rt_hit* device_out, void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

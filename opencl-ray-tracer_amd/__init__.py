@@ -32,6 +32,7 @@ __all__ = [
     "RAY_DTYPE", "Camera", "cast_rays", "occlude_rays", "camera_rays", "cast_camera",
     "CUBE_BOUND_DTYPE", "build_accel", "accel_kept", "cast_rays_accel", "occlude_rays_accel",
     "cast_camera_accel", "shadow_hits_accel", "bounce_hits_accel", "light_hits_mirrored_accel",
+    "light_camera", "bounce_camera",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -85,6 +86,7 @@ EXPORTED_SYMBOLS = (
     "rt_shadow_hits_accel", "rt_shadow_hits_accel_device", "rt_bounce_hits_accel",
     "rt_bounce_hits_accel_device", "rt_light_hits_mirrored_accel",
     "rt_light_hits_mirrored_accel_device",
+    "rt_light_camera", "rt_light_camera_device", "rt_bounce_camera", "rt_bounce_camera_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -282,6 +284,16 @@ def library() -> ctypes.CDLL:
         "rt_light_hits_mirrored_accel_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(_Scene), vp,
                                                                vp, i32, i32, i32, vp, i32, i32,
                                                                i32, vp, vp]),
+        "rt_light_camera": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.POINTER(_Scene), vp,
+                                           i32, i32, i32, vp, i32, i32, i32, vp]),
+        "rt_light_camera_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera),
+                                                  ctypes.POINTER(_Scene), vp, i32, i32, i32, vp,
+                                                  i32, i32, i32, vp, vp]),
+        "rt_bounce_camera": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.POINTER(_Scene), vp,
+                                            i32, i32, i32, i32, vp]),
+        "rt_bounce_camera_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera),
+                                                   ctypes.POINTER(_Scene), vp, i32, i32, i32, i32,
+                                                   vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -977,6 +989,54 @@ def light_hits_mirrored_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray,
     return out
 
 
+def light_camera(camera: Camera, scene: Scene, width: int, height: int, reflectivity=None,
+                 max_bounces: int = 0, shadows: bool = False, fmt: str = "i32x4",
+                 rows: Optional[Tuple[int, int]] = None,
+                 accel: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_light_camera: the camera's view, lit: level 0 of every pixel's chain
+    is cast_camera's hit along the pixel's own ray, and from there the pixel is
+    light_hits_mirrored's (diffuse light, with shadows=True hard shadows,
+    mirror chains of at most `max_bounces` bounces with one `reflectivity` per
+    colour slot); a pixel whose ray meets nothing is (0, 0, 0, 255).  A (rows x
+    width) i32x4 or rgba8 frame.  With `accel` (build_accel(scene)) every walk
+    is the culled one and the frame is the same word for word.  On the host."""
+    if fmt not in ("i32x4", "rgba8"):
+        raise ValueError("light_camera gives an i32x4 or an rgba8 frame")
+    if accel is not None:
+        accel = _accel(accel, scene)
+    rb, re = rows if rows is not None else (0, height)
+    refl = None
+    if reflectivity is not None:
+        refl = np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
+        if refl.size != scene.num_cubes + scene.num_spheres:
+            raise ValueError(f"reflectivity must hold one value per colour slot "
+                             f"({scene.num_cubes + scene.num_spheres}), got {refl.size}")
+    out = np.empty(*_frame_layout(fmt, max(re - rb, 0), max(width, 0)))
+    c, sc = camera.as_c(), scene.as_c()
+    _check(library().rt_light_camera(
+        ctypes.byref(c), ctypes.byref(sc), _ptr(accel), width, rb, re, _ptr(refl),
+        int(max_bounces), int(shadows), _FORMATS[fmt], _ptr(out)), "rt_light_camera")
+    return out
+
+
+def bounce_camera(camera: Camera, scene: Scene, width: int, height: int, bounce: int,
+                  rows: Optional[Tuple[int, int]] = None,
+                  accel: Optional[np.ndarray] = None) -> np.ndarray:
+    """rt_bounce_camera: the HIT_DTYPE frame of bounce number `bounce` of every
+    camera pixel's chain: 0 is cast_camera's frame, 1 .. RT_MAX_BOUNCES the hit
+    of that bounce, followed without regard to reflectivity ((HIT_MISS_T, -1)
+    where it or an earlier level met nothing).  With `accel` every walk is the
+    culled one.  On the host."""
+    if accel is not None:
+        accel = _accel(accel, scene)
+    rb, re = rows if rows is not None else (0, height)
+    out = np.empty((max(re - rb, 0), max(width, 0)), HIT_DTYPE)
+    c, sc = camera.as_c(), scene.as_c()
+    _check(library().rt_bounce_camera(ctypes.byref(c), ctypes.byref(sc), _ptr(accel), width, rb,
+                                      re, int(bounce), _ptr(out)), "rt_bounce_camera")
+    return out
+
+
 def _device_scene(device_scene: dict) -> _Scene:
     """rt_scene of device addresses, lights included (hit post-passes)."""
     g = device_scene.get
@@ -1309,6 +1369,32 @@ class RayTracer:
             rows[0], rows[1], reflectivity_ptr or None, int(max_bounces), int(shadows),
             _FORMATS[fmt], out_ptr or None, stream or None),
             "rt_light_hits_mirrored_accel_device")
+
+    def light_camera_device(self, camera: Camera, device_scene: dict, accel_ptr: int, width: int,
+                            rows: Tuple[int, int], refl_ptr: int, max_bounces: int,
+                            out_ptr: int, fmt: str = "i32x4", shadows: bool = False,
+                            stream: int = 0) -> None:
+        """rt_light_camera_device: light_camera's frame of rows [rows[0],
+        rows[1]) at `out_ptr`, from device pointers; `accel_ptr` 0: unculled,
+        else the records of build_accel_device.  One launch, no hit frame,
+        asynchronous on `stream`."""
+        if fmt not in ("i32x4", "rgba8"):
+            raise ValueError("light_camera_device gives an i32x4 or an rgba8 frame")
+        c, sc = camera.as_c(), _device_scene(device_scene)
+        _check(library().rt_light_camera_device(
+            self._ctx, ctypes.byref(c), ctypes.byref(sc), accel_ptr or None, width, rows[0],
+            rows[1], refl_ptr or None, int(max_bounces), int(shadows), _FORMATS[fmt],
+            out_ptr or None, stream or None), "rt_light_camera_device")
+
+    def bounce_camera_device(self, camera: Camera, device_scene: dict, accel_ptr: int, width: int,
+                             rows: Tuple[int, int], bounce: int, out_ptr: int,
+                             stream: int = 0) -> None:
+        """rt_bounce_camera_device: bounce_camera's frame at `out_ptr`, from
+        device pointers.  One launch, asynchronous on `stream`."""
+        c, sc = camera.as_c(), _device_scene(device_scene)
+        _check(library().rt_bounce_camera_device(
+            self._ctx, ctypes.byref(c), ctypes.byref(sc), accel_ptr or None, width, rows[0],
+            rows[1], int(bounce), out_ptr or None, stream or None), "rt_bounce_camera_device")
 
     def bind_render_device(self, device_scene: dict, width: int, height: int,
                            rows: Tuple[int, int], out_ptr: int,

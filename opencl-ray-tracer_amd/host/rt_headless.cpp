@@ -11,7 +11,8 @@
 //               [--synthetic N M k] [--rows A B] [--ppm out.ppm] [--repeat R]
 //               [--bands B] [--devices D] [--device-scene]
 //               [--format i32x4|rgba8|hit] [--throughput F [--inflight S]]
-//               [--known-answer] [--pick X,Y] [--camera EX,EY,EZ,TX,TY,TZ,FOVY [--accel]]
+//               [--known-answer] [--pick X,Y] [--camera EX,EY,EZ,TX,TY,TZ,FOVY [--accel]
+//                [--light X,Y,Z]... [--mirror R,DEPTH] [--shadows]]
 //
 // --camera (one band, no --device-scene / --throughput): a perspective view
 // instead of the reference's orthographic one.  A pinhole at (EX, EY, EZ)
@@ -25,6 +26,12 @@
 // --accel (with --camera): the cube records are built on the device
 // (rt_accel_build_device) and the culled cast rt_cast_camera_accel_device
 // casts the frame; the frame is the same, byte for byte.
+// --light X,Y,Z (repeatable), --mirror R,DEPTH, --shadows (with --camera,
+// --format i32x4 or rgba8): the view lit.  The lights and a reflectivity of R
+// for every object are uploaded with the scene and the frame comes from one
+// rt_light_camera_device launch (diffuse light, with --shadows hard shadows,
+// mirror chains of at most DEPTH bounces; rt_hip.h), culled with --accel; no
+// hit frame exists.  Without any of the three --camera is as above.
 //
 // --known-answer (reference scene 1, 2 or 3, 640x480, int32x4, the whole
 // frame, seed 1): checks the frame against the reference's own CPU frame as
@@ -228,6 +235,55 @@ int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int w
     return status;
 }
 
+// --camera with --light / --mirror / --shadows: the scene, the lights and the
+// reflectivity `mirror_r` for every object uploaded, one rt_light_camera_device
+// launch over the band's rows into `pixels` (`fmt`: int32x4 or RGBA8).
+// `accel`: the cube records built on the device first, every walk culled.
+int render_camera_lit(Band& band, const rt_scene& scene, const rt_camera& cam, int width,
+                      int32_t fmt, bool accel, const std::vector<float>& lights, float mirror_r,
+                      int mirror_depth, bool shadows, std::vector<int32_t>& pixels) {
+    const size_t ns = (size_t)scene.num_spheres, nc = (size_t)scene.num_cubes;
+    float *so = nullptr, *sr = nullptr, *sc = nullptr, *cv = nullptr, *cc = nullptr;
+    float *li = nullptr, *refl = nullptr;
+    int32_t* out = nullptr;
+    rt_cube_bound* bounds = nullptr;
+    const std::vector<float> r(ns + nc, mirror_r);
+    auto upload = [](float** dev, const float* host, size_t floats) {
+        if (floats == 0) return true;  // (an empty array stays NULL)
+        return hipMalloc(dev, floats * sizeof(float)) == hipSuccess &&
+               hipMemcpy(*dev, host, floats * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    };
+    int status = 1;
+    if (upload(&so, scene.sphere_origins, 4 * ns) && upload(&sr, scene.sphere_radius, ns) &&
+        upload(&sc, scene.sphere_colours, 4 * ns) && upload(&cv, scene.cube_vertices, 144 * nc) &&
+        upload(&cc, scene.cube_colours, 4 * nc) && upload(&li, lights.data(), lights.size()) &&
+        upload(&refl, r.data(), r.size()) &&
+        (!accel || nc == 0 || hipMalloc(&bounds, nc * sizeof(rt_cube_bound)) == hipSuccess) &&
+        hipMalloc(&out, pixels.size() * sizeof(int32_t)) == hipSuccess) {
+        const rt_scene dev{so, sr, sc, scene.num_spheres, cv, cc, scene.num_cubes, li,
+                           (int32_t)(lights.size() / 4)};
+        int rc = accel ? rt_accel_build_device(band.ctx, &dev, bounds, nullptr) : RT_OK;
+        if (rc == RT_OK)
+            rc = rt_light_camera_device(band.ctx, &cam, &dev, bounds, width, band.row_begin,
+                                        band.row_end, refl, mirror_depth, shadows ? 1 : 0, fmt,
+                                        out, nullptr);
+        if (rc == RT_OK && (hipDeviceSynchronize() != hipSuccess ||
+                            hipMemcpy(pixels.data(), out, pixels.size() * sizeof(int32_t),
+                                      hipMemcpyDeviceToHost) != hipSuccess))
+            rc = RT_ERR_HIP;
+        if (rc == RT_OK)
+            status = 0;
+        else
+            std::fprintf(stderr, "camera light pass failed: %s\n", rt_error_string(rc));
+    } else {
+        std::fprintf(stderr, "scene upload failed\n");
+    }
+    for (void* p : {(void*)so, (void*)sr, (void*)sc, (void*)cv, (void*)cc, (void*)li, (void*)refl,
+                    (void*)out, (void*)bounds})
+        if (p) (void)hipFree(p);
+    return status;
+}
+
 // --throughput: S slots round-robin over `frames` timed frames.
 int throughput(int device, int width, int height, int n, int m, unsigned seed, float k,
                const float ray_dir[4], int32_t fmt, int frames, int slots) {
@@ -346,6 +402,10 @@ int main(int argc, char** argv) {
     int pick_x = -1, pick_y = -1;
     bool camera = false, accel = false;
     float cam_v[7] = {};
+    std::vector<float> lights;  // float4 each
+    float mirror_r = 0.0f;
+    int mirror_depth = 0;
+    bool lit = false, shadows = false;
     std::string ppm;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -393,6 +453,27 @@ int main(int argc, char** argv) {
         }
         else if (a == "--accel")
             accel = true;
+        else if (a == "--shadows")
+            lit = shadows = true;
+        else if (a == "--light") {
+            float l[3];
+            if (std::sscanf(next(), "%f,%f,%f", &l[0], &l[1], &l[2]) != 3) {
+                std::fprintf(stderr, "--light takes X,Y,Z\n");
+                return 2;
+            }
+            lights.insert(lights.end(), {l[0], l[1], l[2], 1.0f});
+            lit = true;
+        }
+        else if (a == "--mirror") {
+            if (std::sscanf(next(), "%f,%d", &mirror_r, &mirror_depth) != 2 ||
+                !(mirror_r >= 0.0f && mirror_r <= 1.0f) || mirror_depth < 0 ||
+                mirror_depth > RT_MAX_BOUNCES) {
+                std::fprintf(stderr, "--mirror takes R,DEPTH with 0 <= R <= 1 and 0 <= DEPTH <= %d\n",
+                             RT_MAX_BOUNCES);
+                return 2;
+            }
+            lit = true;
+        }
         else if (a == "--camera") {
             camera = std::sscanf(next(), "%f,%f,%f,%f,%f,%f,%f", &cam_v[0], &cam_v[1], &cam_v[2],
                                  &cam_v[3], &cam_v[4], &cam_v[5], &cam_v[6]) == 7;
@@ -430,6 +511,11 @@ int main(int argc, char** argv) {
     }
     if (accel && !camera) {
         std::fprintf(stderr, "--accel needs --camera\n");
+        return 2;
+    }
+    if (lit && (!camera || fmt == RT_FORMAT_HIT)) {
+        std::fprintf(stderr, "--light, --mirror and --shadows need --camera and --format i32x4 "
+                             "or rgba8\n");
         return 2;
     }
     rt_camera cam{};
@@ -513,7 +599,9 @@ int main(int argc, char** argv) {
     int status = 0;
     if (camera) {
         std::printf("HIP Ray Tracer Begin\n");
-        status = render_camera(bands[0], scene, cam, width, fmt, accel, pixels);
+        status = lit ? render_camera_lit(bands[0], scene, cam, width, fmt, accel, lights, mirror_r,
+                                         mirror_depth, shadows, pixels)
+                     : render_camera(bands[0], scene, cam, width, fmt, accel, pixels);
         if (status == 0)
             std::printf("camera eye (%g, %g, %g) target (%g, %g, %g) fov %g: one ray per pixel\n",
                         (double)cam_v[0], (double)cam_v[1], (double)cam_v[2], (double)cam_v[3],
