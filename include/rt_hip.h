@@ -850,6 +850,92 @@ int rt_bounce_camera_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene
                             const rt_cube_bound* device_accel, int32_t width, int32_t row_begin,
                             int32_t row_end, int32_t bounce, rt_hit* device_out, void* stream);
 
+/* ---- ray queries culled by spatially grouped sphere bounds - */
+/* The *_accel queries above still test every ray against every sphere.  A
+ * caller may also build one 64-byte record per group of up to 8 nearby spheres
+ * and pass the records to the *_grouped forms of the three queries: a group
+ * whose record proves that none of its members can be accepted for a ray is
+ * left out for that ray.  The results are the unculled and the *_accel calls'
+ * results word for word, on every input: a group is kept
+ * whenever a miss is not proven, always for a non-finite ray, for a group with
+ * a non-finite member, and outside the magnitudes stated there.
+ *
+ * rt_sphere_group: the spheres are ordered by (Morton key of the centre, index)
+ * and cut into runs of `group_size`; a record holds the box of its members
+ * (lo = min of centre - |r| rounded down, hi = max of centre + |r| rounded up),
+ * the largest |r|, and the members' indices in ascending order (unused slots
+ * -1).  A group with a non-finite centre or radius has lo = -inf, hi = +inf,
+ * rmax = +inf.  The build is written operation by operation in §3.1j; host and
+ * device records are bit-identical.  Rebuild after any change of the spheres.
+ * rt_sphere_groups_count: ceil(num_spheres / group_size) records, or -1 for
+ * num_spheres < 0 or group_size outside 1..8.
+ * rt_sphere_groups_workspace_bytes: the device build's workspace for
+ * num_spheres spheres (16 + 8 * num_spheres, rounded up to 16; -1 for
+ * num_spheres < 0).
+ * rt_sphere_groups_build_device: four launches on `stream`, in order (the
+ * bounds of the centres, the keys, the ranks, the records); the ranks count
+ * over all keys, num_spheres^2 compares (16 M at 4096 spheres).  No allocation:
+ * `device_workspace` is the caller's, 16-byte aligned, at least
+ * rt_sphere_groups_workspace_bytes(num_spheres) bytes, and may be reused once
+ * the work on `stream` in front of that reuse is ordered behind the build.
+ * rt_*_grouped*: the *_accel call's arguments and contract, plus `groups`,
+ * `num_groups` directly after `accel`: the records rt_sphere_groups_build*
+ * wrote for THIS scene's spheres.  A stale or foreign record is not detectable
+ * and gives wrong results (a member index outside the scene is skipped).
+ * rt_sphere_groups_kept: per ray the number of groups the keep test keeps
+ * (segment = 0: the cast's test, 1: the occlusion test's); host only.
+ *
+ * RT_ERR_INVALID_ARG: what the *_accel call refuses; group_size outside 1..8;
+ * with num_spheres > 0 a NULL or misaligned (16 bytes) groups / out /
+ * workspace, a workspace too small, or num_groups that is not
+ * rt_sphere_groups_count(num_spheres, g) for any g in 1..8; num_groups != 0
+ * with num_spheres == 0; segment other than 0 or 1.  num_spheres == 0: RT_OK,
+ * groups / out / workspace may be NULL, the build launches nothing.  Device
+ * calls: checked before any HIP call; asynchronous on `stream`; the queries
+ * are one launch, no workspace, no allocation. */
+typedef struct rt_sphere_group { /* 64 bytes; arrays of them 16-byte aligned */
+    float lo[3];
+    float rmax;
+    float hi[3];
+    int32_t count;             /* members, 1..8 */
+    int32_t member[8];         /* ascending sphere indices, then -1 */
+} rt_sphere_group;
+
+int32_t rt_sphere_groups_count(int32_t num_spheres, int32_t group_size);
+int64_t rt_sphere_groups_workspace_bytes(int32_t num_spheres);
+int rt_sphere_groups_build(const rt_scene* scene, int32_t group_size, rt_sphere_group* out);
+int rt_sphere_groups_build_device(rt_ctx* ctx, const rt_scene* device_scene, int32_t group_size,
+                                  rt_sphere_group* device_out, void* device_workspace,
+                                  int64_t workspace_bytes, void* stream);
+int rt_sphere_groups_kept(const rt_ray* rays, int64_t n, const rt_scene* scene,
+                          const rt_sphere_group* groups, int32_t num_groups, int32_t segment,
+                          int32_t* out_count);
+int rt_cast_rays_grouped(const rt_ray* rays, int64_t n, const rt_scene* scene,
+                         const rt_cube_bound* accel, const rt_sphere_group* groups,
+                         int32_t num_groups, rt_hit* out_hits, int32_t* out_triangle);
+int rt_occlude_rays_grouped(const rt_ray* rays, int64_t n, const rt_scene* scene,
+                            const rt_cube_bound* accel, const rt_sphere_group* groups,
+                            int32_t num_groups, uint8_t* out_occluded);
+int rt_cast_camera_grouped(const rt_camera* camera, const rt_scene* scene,
+                           const rt_cube_bound* accel, const rt_sphere_group* groups,
+                           int32_t num_groups, int32_t width, int32_t row_begin, int32_t row_end,
+                           rt_hit* out_hits, int32_t* out_triangle);
+int rt_cast_rays_grouped_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                                const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                                const rt_sphere_group* device_groups, int32_t num_groups,
+                                rt_hit* device_out_hits, int32_t* device_out_triangle,
+                                void* stream);
+int rt_occlude_rays_grouped_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
+                                   const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                                   const rt_sphere_group* device_groups, int32_t num_groups,
+                                   uint8_t* device_out_occluded, void* stream);
+int rt_cast_camera_grouped_device(rt_ctx* ctx, const rt_camera* camera,
+                                  const rt_scene* device_scene, const rt_cube_bound* device_accel,
+                                  const rt_sphere_group* device_groups, int32_t num_groups,
+                                  int32_t width, int32_t row_begin, int32_t row_end,
+                                  rt_hit* device_out_hits, int32_t* device_out_triangle,
+                                  void* stream);
+
 /* Known-answer checksum of a frame: FNV-1a-64 over its 32-bit words in
  * memory order (`h ^= w; h *= 0x100000001b3`), starting from `basis`
  * (RT_FNV1A64_BASIS; the survey's probe of the reference's CPU frames,

@@ -33,6 +33,8 @@ __all__ = [
     "CUBE_BOUND_DTYPE", "build_accel", "accel_kept", "cast_rays_accel", "occlude_rays_accel",
     "cast_camera_accel", "shadow_hits_accel", "bounce_hits_accel", "light_hits_mirrored_accel",
     "light_camera", "bounce_camera",
+    "SPHERE_GROUP_DTYPE", "build_sphere_groups", "sphere_groups_kept", "cast_rays_grouped",
+    "occlude_rays_grouped", "cast_camera_grouped",
 ]
 
 PKG_DIR = Path(__file__).resolve().parent
@@ -59,6 +61,11 @@ RAY_DTYPE = np.dtype([("ox", "<f4"), ("oy", "<f4"), ("oz", "<f4"), ("skip", "<i4
 # *_accel ray queries: its box, its largest squared edge, its triangles' normals.
 CUBE_BOUND_DTYPE = np.dtype([("lo", "<f4", (3,)), ("emax2", "<f4"), ("hi", "<f4", (3,)),
                              ("reserved", "<f4"), ("normal", "<f8", (12, 3))])
+# rt_sphere_group (include/rt_hip.h): one group of up to 8 nearby spheres of
+# build_sphere_groups, for the *_grouped ray queries: the members' box, their
+# largest |radius|, their count and their ascending indices (unused slots -1).
+SPHERE_GROUP_DTYPE = np.dtype([("lo", "<f4", (3,)), ("rmax", "<f4"), ("hi", "<f4", (3,)),
+                               ("count", "<i4"), ("member", "<i4", (8,))])
 _PATHS = {"auto": RT_PATH_AUTO, "binned": RT_PATH_BINNED, "generic": RT_PATH_GENERIC}
 
 # Every symbol include/rt_hip.h declares (tests check the .so exports them).
@@ -87,6 +94,10 @@ EXPORTED_SYMBOLS = (
     "rt_bounce_hits_accel_device", "rt_light_hits_mirrored_accel",
     "rt_light_hits_mirrored_accel_device",
     "rt_light_camera", "rt_light_camera_device", "rt_bounce_camera", "rt_bounce_camera_device",
+    "rt_sphere_groups_count", "rt_sphere_groups_workspace_bytes", "rt_sphere_groups_build",
+    "rt_sphere_groups_build_device", "rt_sphere_groups_kept", "rt_cast_rays_grouped",
+    "rt_occlude_rays_grouped", "rt_cast_camera_grouped", "rt_cast_rays_grouped_device",
+    "rt_occlude_rays_grouped_device", "rt_cast_camera_grouped_device",
 )
 # rt_last_kernel's codes (RT_KERNEL_*, rt_hip.h) by name
 KERNEL_NAMES = {0: None, 1: "trace3_kernel", 2: "trace_small_kernel", 3: "frame_small_kernel",
@@ -294,6 +305,28 @@ def library() -> ctypes.CDLL:
         "rt_bounce_camera_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera),
                                                    ctypes.POINTER(_Scene), vp, i32, i32, i32, i32,
                                                    vp, vp]),
+        "rt_sphere_groups_count": (i32, [i32, i32]),
+        "rt_sphere_groups_workspace_bytes": (ctypes.c_int64, [i32]),
+        "rt_sphere_groups_build": (ctypes.c_int, [ctypes.POINTER(_Scene), i32, vp]),
+        "rt_sphere_groups_build_device": (ctypes.c_int, [vp, ctypes.POINTER(_Scene), i32, vp, vp,
+                                                         ctypes.c_int64, vp]),
+        "rt_sphere_groups_kept": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp,
+                                                 i32, i32, vp]),
+        "rt_cast_rays_grouped": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp,
+                                                vp, i32, vp, vp]),
+        "rt_occlude_rays_grouped": (ctypes.c_int, [vp, ctypes.c_int64, ctypes.POINTER(_Scene), vp,
+                                                   vp, i32, vp]),
+        "rt_cast_camera_grouped": (ctypes.c_int, [ctypes.POINTER(_Camera), ctypes.POINTER(_Scene),
+                                                  vp, vp, i32, i32, i32, i32, vp, vp]),
+        "rt_cast_rays_grouped_device": (ctypes.c_int, [vp, vp, ctypes.c_int64,
+                                                       ctypes.POINTER(_Scene), vp, vp, i32, vp,
+                                                       vp, vp]),
+        "rt_occlude_rays_grouped_device": (ctypes.c_int, [vp, vp, ctypes.c_int64,
+                                                          ctypes.POINTER(_Scene), vp, vp, i32, vp,
+                                                          vp]),
+        "rt_cast_camera_grouped_device": (ctypes.c_int, [vp, ctypes.POINTER(_Camera),
+                                                         ctypes.POINTER(_Scene), vp, vp, i32, i32,
+                                                         i32, i32, vp, vp, vp]),
         "rt_selftest_fp32": (ctypes.c_int, [vp, vp, i32, vp, vp]),
         "rt_debug_triangle_box": (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
         "rt_debug_sphere_box": (ctypes.c_int, [vp, f32, vp, i32, i32, i32, vp, vp]),
@@ -930,6 +963,87 @@ def cast_camera_accel(camera: Camera, scene: Scene, accel: np.ndarray, width: in
     return (out, tri) if triangles else out
 
 
+def _groups(groups: np.ndarray) -> np.ndarray:
+    groups = np.ascontiguousarray(groups)
+    if groups.dtype != SPHERE_GROUP_DTYPE or groups.ndim != 1:
+        raise ValueError(f"groups must be build_sphere_groups(scene)'s array, got {groups.dtype} "
+                         f"{groups.shape}")
+    return groups
+
+
+def build_sphere_groups(scene: Scene, group_size: int = 8) -> np.ndarray:
+    """rt_sphere_groups_build: one SPHERE_GROUP_DTYPE record per run of
+    `group_size` (1..8) spheres of `scene` in the order of their centres along
+    a Morton curve, for the *_grouped ray queries.  Build once per scene;
+    rebuild after any change of the spheres (a stale record gives wrong
+    results).  On the host."""
+    count = library().rt_sphere_groups_count(scene.num_spheres, int(group_size))
+    out = np.zeros(max(count, 0), SPHERE_GROUP_DTYPE)
+    sc = scene.as_c()
+    _check(library().rt_sphere_groups_build(ctypes.byref(sc), int(group_size), _ptr(out)),
+           "rt_sphere_groups_build")
+    return out
+
+
+def sphere_groups_kept(rays: np.ndarray, scene: Scene, groups: np.ndarray,
+                       segment: bool = False) -> np.ndarray:
+    """rt_sphere_groups_kept: per ray the int32 number of groups that the keep
+    test keeps (segment=False: cast_rays_grouped's test, True:
+    occlude_rays_grouped's).  On the host."""
+    rays, groups = _rays(rays), _groups(groups)
+    out = np.empty(rays.shape, np.int32)
+    sc = scene.as_c()
+    _check(library().rt_sphere_groups_kept(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(groups),
+                                           groups.size, int(bool(segment)), _ptr(out)),
+           "rt_sphere_groups_kept")
+    return out
+
+
+def cast_rays_grouped(rays: np.ndarray, scene: Scene, accel: np.ndarray, groups: np.ndarray,
+                      triangles: bool = False):
+    """rt_cast_rays_grouped: cast_rays' result word for word, culled by `accel`
+    (build_accel(scene)) and with the sphere groups that `groups`
+    (build_sphere_groups(scene)) proves missed left out per ray.  On the host."""
+    rays, accel, groups = _rays(rays), _accel(accel, scene), _groups(groups)
+    out = np.empty(rays.shape, HIT_DTYPE)
+    tri = np.empty(rays.shape, np.int32) if triangles else None
+    sc = scene.as_c()
+    _check(library().rt_cast_rays_grouped(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
+                                          _ptr(groups), groups.size, _ptr(out), _ptr(tri)),
+           "rt_cast_rays_grouped")
+    return (out, tri) if triangles else out
+
+
+def occlude_rays_grouped(rays: np.ndarray, scene: Scene, accel: np.ndarray,
+                         groups: np.ndarray) -> np.ndarray:
+    """rt_occlude_rays_grouped: occlude_rays' result word for word, culled by
+    `accel` and `groups`.  On the host."""
+    rays, accel, groups = _rays(rays), _accel(accel, scene), _groups(groups)
+    out = np.empty(rays.shape, np.uint8)
+    sc = scene.as_c()
+    _check(library().rt_occlude_rays_grouped(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
+                                             _ptr(groups), groups.size, _ptr(out)),
+           "rt_occlude_rays_grouped")
+    return out
+
+
+def cast_camera_grouped(camera: Camera, scene: Scene, accel: np.ndarray, groups: np.ndarray,
+                        width: int, height: int, rows: Optional[Tuple[int, int]] = None,
+                        triangles: bool = False):
+    """rt_cast_camera_grouped: cast_camera's frame word for word, culled by
+    `accel` and `groups`.  On the host."""
+    accel, groups = _accel(accel, scene), _groups(groups)
+    rb, re = rows if rows is not None else (0, height)
+    shape = (max(re - rb, 0), max(width, 0))
+    out = np.empty(shape, HIT_DTYPE)
+    tri = np.empty(shape, np.int32) if triangles else None
+    c, sc = camera.as_c(), scene.as_c()
+    _check(library().rt_cast_camera_grouped(ctypes.byref(c), ctypes.byref(sc), _ptr(accel),
+                                            _ptr(groups), groups.size, width, rb, re, _ptr(out),
+                                            _ptr(tri)), "rt_cast_camera_grouped")
+    return (out, tri) if triangles else out
+
+
 def shadow_hits_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray,
                       rows: Optional[Tuple[int, int]] = None,
                       ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
@@ -1327,6 +1441,55 @@ class RayTracer:
             self._ctx, ctypes.byref(c), ctypes.byref(sc), accel_ptr or None, width, rows[0],
             rows[1], hits_ptr or None, triangles_ptr or None, stream or None),
             "rt_cast_camera_accel_device")
+
+    def build_sphere_groups_device(self, device_scene: dict, group_size: int, out_ptr: int,
+                                   workspace_ptr: int, workspace_bytes: int,
+                                   stream: int = 0) -> None:
+        """rt_sphere_groups_build_device: one rt_sphere_group (64 bytes) per
+        run of `group_size` spheres of the device scene at `out_ptr`, bit for
+        bit build_sphere_groups' records.  `workspace_ptr`: the caller's
+        16-byte aligned device memory of at least
+        rt_sphere_groups_workspace_bytes(num_spheres) bytes.  Four launches,
+        asynchronous on `stream`, no allocation."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_sphere_groups_build_device(
+            self._ctx, ctypes.byref(sc), int(group_size), out_ptr or None, workspace_ptr or None,
+            int(workspace_bytes), stream or None), "rt_sphere_groups_build_device")
+
+    def cast_rays_grouped_device(self, rays_ptr: int, n: int, device_scene: dict, accel_ptr: int,
+                                 groups_ptr: int, num_groups: int, hits_ptr: int,
+                                 triangles_ptr: int = 0, stream: int = 0) -> None:
+        """rt_cast_rays_grouped_device: cast_rays_accel_device, the spheres
+        culled by the `num_groups` records at `groups_ptr`
+        (build_sphere_groups_device's, of this scene).  Asynchronous."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_cast_rays_grouped_device(
+            self._ctx, rays_ptr or None, n, ctypes.byref(sc), accel_ptr or None,
+            groups_ptr or None, num_groups, hits_ptr or None, triangles_ptr or None,
+            stream or None), "rt_cast_rays_grouped_device")
+
+    def occlude_rays_grouped_device(self, rays_ptr: int, n: int, device_scene: dict,
+                                    accel_ptr: int, groups_ptr: int, num_groups: int,
+                                    out_ptr: int, stream: int = 0) -> None:
+        """rt_occlude_rays_grouped_device: occlude_rays_accel_device, the
+        spheres culled by the records at `groups_ptr`.  Asynchronous."""
+        sc = _device_scene(device_scene)
+        _check(library().rt_occlude_rays_grouped_device(
+            self._ctx, rays_ptr or None, n, ctypes.byref(sc), accel_ptr or None,
+            groups_ptr or None, num_groups, out_ptr or None, stream or None),
+            "rt_occlude_rays_grouped_device")
+
+    def cast_camera_grouped_device(self, camera: Camera, device_scene: dict, accel_ptr: int,
+                                   groups_ptr: int, num_groups: int, width: int,
+                                   rows: Tuple[int, int], hits_ptr: int, triangles_ptr: int = 0,
+                                   stream: int = 0) -> None:
+        """rt_cast_camera_grouped_device: cast_camera_accel_device, the
+        spheres culled by the records at `groups_ptr`.  Asynchronous."""
+        c, sc = camera.as_c(), _device_scene(device_scene)
+        _check(library().rt_cast_camera_grouped_device(
+            self._ctx, ctypes.byref(c), ctypes.byref(sc), accel_ptr or None, groups_ptr or None,
+            num_groups, width, rows[0], rows[1], hits_ptr or None, triangles_ptr or None,
+            stream or None), "rt_cast_camera_grouped_device")
 
     def shadow_hits_accel_device(self, hits_ptr: int, device_scene: dict, accel_ptr: int,
                                  width: int, rows: Tuple[int, int], out_ptr: int,

@@ -11,8 +11,8 @@
 //               [--synthetic N M k] [--rows A B] [--ppm out.ppm] [--repeat R]
 //               [--bands B] [--devices D] [--device-scene]
 //               [--format i32x4|rgba8|hit] [--throughput F [--inflight S]]
-//               [--known-answer] [--pick X,Y] [--camera EX,EY,EZ,TX,TY,TZ,FOVY [--accel]
-//                [--light X,Y,Z]... [--mirror R,DEPTH] [--shadows]]
+//               [--known-answer] [--pick X,Y] [--camera EX,EY,EZ,TX,TY,TZ,FOVY [--accel
+//                [--groups]] [--light X,Y,Z]... [--mirror R,DEPTH] [--shadows]]
 //
 // --camera (one band, no --device-scene / --throughput): a perspective view
 // instead of the reference's orthographic one.  A pinhole at (EX, EY, EZ)
@@ -26,6 +26,9 @@
 // --accel (with --camera): the cube records are built on the device
 // (rt_accel_build_device) and the culled cast rt_cast_camera_accel_device
 // casts the frame; the frame is the same, byte for byte.
+// --groups (with --camera --accel, no lit view): the spheres' group records
+// are built on the device too (rt_sphere_groups_build_device, groups of 8) and
+// rt_cast_camera_grouped_device casts the frame; the same frame again.
 // --light X,Y,Z (repeatable), --mirror R,DEPTH, --shadows (with --camera,
 // --format i32x4 or rgba8): the view lit.  The lights and a reflectivity of R
 // for every object are uploaded with the scene and the frame comes from one
@@ -180,14 +183,21 @@ int render_device_scene(Band& band, int width, int height, int row_begin, int ro
 // --camera: the scene uploaded, one rt_cast_camera_device launch over the
 // band's rows, the hit frame read back and shaded into `pixels` (`fmt`).
 // `accel`: the cube records built on the device first (rt_accel_build_device)
-// and the culled cast (rt_cast_camera_accel_device): the same frame.
+// and the culled cast (rt_cast_camera_accel_device): the same frame.  `groups`
+// (with `accel`): the spheres' group records built on the device as well and the
+// cast culled by both (rt_cast_camera_grouped_device): the same frame.
 int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int width,
-                  int32_t fmt, bool accel, std::vector<int32_t>& pixels) {
+                  int32_t fmt, bool accel, bool groups, std::vector<int32_t>& pixels) {
     const size_t px = (size_t)width * (size_t)(band.row_end - band.row_begin);
     const size_t ns = (size_t)scene.num_spheres, nc = (size_t)scene.num_cubes;
     float *so = nullptr, *sr = nullptr, *sc = nullptr, *cv = nullptr, *cc = nullptr;
     rt_hit* out = nullptr;
     rt_cube_bound* bounds = nullptr;
+    rt_sphere_group* records = nullptr;
+    void* workspace = nullptr;
+    const int32_t group_size = 8;
+    const int32_t num_groups = groups ? rt_sphere_groups_count(scene.num_spheres, group_size) : 0;
+    const int64_t ws_bytes = rt_sphere_groups_workspace_bytes(scene.num_spheres);
     std::vector<rt_hit> hits(px);
     auto upload = [](float** dev, const float* host, size_t floats) {
         if (floats == 0) return true;  // (an empty array stays NULL)
@@ -199,12 +209,22 @@ int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int w
         upload(&sc, scene.sphere_colours, 4 * ns) && upload(&cv, scene.cube_vertices, 144 * nc) &&
         upload(&cc, scene.cube_colours, 4 * nc) &&
         (!accel || nc == 0 || hipMalloc(&bounds, nc * sizeof(rt_cube_bound)) == hipSuccess) &&
+        (num_groups == 0 ||
+         (hipMalloc(&records, (size_t)num_groups * sizeof(rt_sphere_group)) == hipSuccess &&
+          hipMalloc(&workspace, (size_t)ws_bytes) == hipSuccess)) &&
         hipMalloc(&out, px * sizeof(rt_hit)) == hipSuccess) {
         const rt_scene dev{so, sr, sc, scene.num_spheres, cv, cc, scene.num_cubes, nullptr, 0};
         int rc;
         if (accel) {
             rc = rt_accel_build_device(band.ctx, &dev, bounds, nullptr);
-            if (rc == RT_OK)
+            if (rc == RT_OK && groups) {
+                rc = rt_sphere_groups_build_device(band.ctx, &dev, group_size, records, workspace,
+                                                   ws_bytes, nullptr);
+                if (rc == RT_OK)
+                    rc = rt_cast_camera_grouped_device(band.ctx, &cam, &dev, bounds, records,
+                                                       num_groups, width, band.row_begin,
+                                                       band.row_end, out, nullptr, nullptr);
+            } else if (rc == RT_OK)
                 rc = rt_cast_camera_accel_device(band.ctx, &cam, &dev, bounds, width,
                                                  band.row_begin, band.row_end, out, nullptr,
                                                  nullptr);
@@ -230,7 +250,7 @@ int render_camera(Band& band, const rt_scene& scene, const rt_camera& cam, int w
         std::fprintf(stderr, "scene upload failed\n");
     }
     for (void* p : {(void*)so, (void*)sr, (void*)sc, (void*)cv, (void*)cc, (void*)out,
-                    (void*)bounds})
+                    (void*)bounds, (void*)records, workspace})
         if (p) (void)hipFree(p);
     return status;
 }
@@ -400,7 +420,7 @@ int main(int argc, char** argv) {
     int32_t fmt = RT_FORMAT_I32X4;
     bool known_answer = false;
     int pick_x = -1, pick_y = -1;
-    bool camera = false, accel = false;
+    bool camera = false, accel = false, groups = false;
     float cam_v[7] = {};
     std::vector<float> lights;  // float4 each
     float mirror_r = 0.0f;
@@ -453,6 +473,8 @@ int main(int argc, char** argv) {
         }
         else if (a == "--accel")
             accel = true;
+        else if (a == "--groups")
+            groups = true;
         else if (a == "--shadows")
             lit = shadows = true;
         else if (a == "--light") {
@@ -511,6 +533,11 @@ int main(int argc, char** argv) {
     }
     if (accel && !camera) {
         std::fprintf(stderr, "--accel needs --camera\n");
+        return 2;
+    }
+    if (groups && (!accel || lit)) {
+        std::fprintf(stderr, "--groups needs --camera --accel and no --light, --mirror or "
+                             "--shadows\n");
         return 2;
     }
     if (lit && (!camera || fmt == RT_FORMAT_HIT)) {
@@ -601,7 +628,7 @@ int main(int argc, char** argv) {
         std::printf("HIP Ray Tracer Begin\n");
         status = lit ? render_camera_lit(bands[0], scene, cam, width, fmt, accel, lights, mirror_r,
                                          mirror_depth, shadows, pixels)
-                     : render_camera(bands[0], scene, cam, width, fmt, accel, pixels);
+                     : render_camera(bands[0], scene, cam, width, fmt, accel, groups, pixels);
         if (status == 0)
             std::printf("camera eye (%g, %g, %g) target (%g, %g, %g) fov %g: one ray per pixel\n",
                         (double)cam_v[0], (double)cam_v[1], (double)cam_v[2], (double)cam_v[3],
