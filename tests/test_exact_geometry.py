@@ -1,0 +1,840 @@
+"""The host functions of the ray queries and the surfaces against exact geometry
+(tests/exact_ref.py), without a GPU.
+
+Outputs are judged by meaning, not as words: on a *decided* ray the object is
+the exact one, t is within the derived tolerance and the
+triangle is one whose exact test is a clear or borderline candidate at that t;
+a clear miss is (300000, -1).  Borderline and undecided rays are excluded and
+counted, and the counts are capped on the reference alone, before the library
+is called.
+
+What is left out, on purpose.  Bounces beyond the first: each level starts
+from a rounded point along a rounded direction, the errors compound, and no
+band derived here covers them.  The shadow segments and the first bounce are
+judged from the float32 hit point fl(o + t*d) itself, taken as an exact real:
+that is the segment the library is asked about, so no band is widened by the
+hit point's displacement.  That point is not read from the library, which
+does not return it: `hit_points32` evaluates DESIGN.md §3.1a's two-operation
+formula on the library's t, so the "displacement" that test_hit_surfaces bounds
+is that of the test's own point, i.e. the library's t once more, and the
+frames whose t the segments and the bounce start from are judged by
+judge_cast first.  The rows (4096, 3) and (30000, 3) of the
+one-sphere table lie outside the fp32 quadratic's domain of validity
+(DESIGN.md §3.1f): almost every ray of them is inside the band, so they decide
+almost nothing, and only that is asserted.
+"""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+import exact_ref as ex
+import gpu_support as gs
+import rays_ref as yr  # (the ray record's layout and the seeded rays; no arithmetic)
+
+F32 = np.float32
+U = ex.U32
+_CACHE = {}
+
+
+# ---------------------------------------------------------------------------
+# Scenes
+# ---------------------------------------------------------------------------
+WHITE = (1, 1, 1, 255)
+CENTRE = (48.5, 37.25, -60.125)
+ROTATED = [("scale", 9, 7, 5), ("rotate", 0.3, 0.7, 0.1)]
+
+
+def one_sphere(pkg, r, centre=CENTRE):
+    return gs.scene_from(pkg, spheres=[((*centre, 1), r, WHITE)])
+
+
+def cube_and_sphere(pkg, cube_z, sphere_z):
+    return gs.scene_from(pkg, spheres=[((40, 30, sphere_z, 1), 8, WHITE)],
+                         cubes=[(ROTATED + [("translate", 40, 30, cube_z)], WHITE)])
+
+
+def scaled_scene(pkg):
+    """A cube, a sphere, and a cube of edge 0.05 whose |det| falls below 1e-6
+    for directions of length 1e-4."""
+    return gs.scene_from(pkg, spheres=[((60, 30, -40, 1), 8, WHITE)],
+                         cubes=[(ROTATED + [("translate", 30, 30, -40)], WHITE),
+                                ([("scale", 0.025, 0.025, 0.025), ("rotate", 0.2, 0.4, 0.1),
+                                  ("translate", 45, 30, -20)], WHITE)])
+
+
+def frame_scene(pkg):
+    """37 x 29: a sphere that holds part of the plane z = 0 (far roots, normals
+    that have to be turned), a sphere, a rotated cube, an axis-aligned cube."""
+    s = gs.scene_from(pkg, spheres=[((8.3, 8.6, -6, 1), 9, WHITE), ((27.4, 9.3, -30, 1), 6, WHITE)],
+                      cubes=[([("scale", 6, 5, 3), ("rotate", 0.4, 0.6, 0.2),
+                               ("translate", 12, 21, -25)], WHITE),
+                             ([("scale", 4.3, 3.4, 2), ("translate", 28.37, 22.61, -40)], WHITE)])
+    return s
+
+
+def shadow_scene(pkg, lights=((18, 14, 30, 1), (14, 16, -5, 1))):
+    """A slab behind the whole 37 x 29 frame with a sphere and a rotated cube
+    in front of it, and two lights that each throw both shadows onto the slab;
+    the second stands beside the two, so that parts of them face away from it."""
+    s = gs.scene_from(pkg, spheres=[((11.3, 9.4, -22, 1), 6, WHITE)],
+                      cubes=[([("scale", 64, 64, 2), ("translate", 16.3, 16, -40)], WHITE),
+                             ([("scale", 5, 4, 3), ("rotate", 0.4, 0.6, 0.2),
+                               ("translate", 26.3, 19.4, -22)], WHITE)])
+    return pkg.Scene(s.sphere_origins, s.sphere_radius, s.sphere_colours, s.cube_vertices,
+                     s.cube_colours, np.asarray(lights, F32).reshape(-1, 4))
+
+
+def flat_mirror_scene(pkg):
+    """An axis-aligned slab behind the whole frame, and behind the plane of the
+    origins (z > 0) a sphere and a rotated cube that only mirrored rays meet."""
+    return gs.scene_from(pkg, spheres=[((40, 8, 30, 1), 7, WHITE)],
+                         cubes=[([("scale", 64, 64, 2), ("translate", 16, 16, -40)], WHITE),
+                                ([("scale", 5, 4, 3), ("rotate", 0.4, 0.6, 0.2),
+                                  ("translate", 30, 2, 35)], WHITE)])
+
+
+MIRROR_DIR = (0.25, -0.125, -1.0, -1.0)
+FRAME_DIRS = {"reference": gs.REF_DIR, "slanted": (0.3, -0.2, -1.0, -1.0)}
+FW, FH = 37, 29
+
+
+# ---------------------------------------------------------------------------
+# Ray families.  kind: "sphere" (at most 10 % excluded), "mixed" (1 %),
+# "edge" (membership instead of exclusion: no cap), "outside" (out of domain).
+# ---------------------------------------------------------------------------
+def aimed(rng, n, centre, spread, distance):
+    """`n` rays from `distance` away from `centre` in a random direction, aimed
+    at a point drawn N(0, spread) about it, |d| in 0.5 .. 200."""
+    u = rng.normal(size=(n, 3))
+    u /= np.linalg.norm(u, axis=1)[:, None]
+    o = np.asarray(centre) + u * np.reshape(distance, (-1, 1))
+    d = np.asarray(centre) + rng.normal(0, spread, (n, 3)) - o
+    d *= (rng.uniform(0.5, 200.0, n) / np.linalg.norm(d, axis=1))[:, None]
+    return o, d
+
+
+def rays_of(o, d, skip=-1):
+    return yr.make_rays(np.asarray(o).T.astype(F32), np.asarray(d).T.astype(F32), skip)
+
+
+def sphere_row(pkg, distance, r, n=3000, seed=1):
+    rng = np.random.default_rng(seed)
+    return one_sphere(pkg, r), rays_of(*aimed(rng, n, CENTRE, 0.8 * r, distance))
+
+
+def along_axis(rng, n, target, spread, z0=25.0, origin_spread=3.0):
+    """Rays from about (target.x, target.y, z0) down the z axis, aimed near `target`."""
+    o = np.array([target[0], target[1], z0]) + rng.normal(0, origin_spread, (n, 3))
+    d = np.asarray(target) + rng.normal(0, spread, (n, 3)) - o
+    d *= (rng.uniform(0.5, 200.0, n) / np.linalg.norm(d, axis=1))[:, None]
+    return o, d
+
+
+def cube_points(scene, rng, n, cube=0, edge=None):
+    """Points on the triangles of a cube: barycentric interior points, or
+    (`edge`: a distance) points that far from an edge, on both sides of it."""
+    tris = ex.Geometry(scene).tris[cube].astype(np.float64)
+    k = rng.integers(0, 12, n)
+    a, b, c = tris[k, 0], tris[k, 1], tris[k, 2]
+    if edge is None:
+        w = rng.dirichlet((1, 1, 1), n)
+        return w[:, :1] * a + w[:, 1:2] * b + w[:, 2:] * c
+    which = rng.integers(0, 3, n)
+    ends = [(a, b, c), (b, c, a), (c, a, b)]  # (edge start, edge end, opposite vertex)
+    p0 = np.select([(which == i)[:, None] for i in range(3)], [e[0] for e in ends])
+    p1 = np.select([(which == i)[:, None] for i in range(3)], [e[1] for e in ends])
+    p2 = np.select([(which == i)[:, None] for i in range(3)], [e[2] for e in ends])
+    s = rng.uniform(0.1, 0.9, (n, 1))
+    on = p0 + s * (p1 - p0)
+    along = (p1 - p0) / np.linalg.norm(p1 - p0, axis=1)[:, None]
+    inward = (p2 - p0) - ((p2 - p0) * along).sum(1)[:, None] * along
+    inward /= np.linalg.norm(inward, axis=1)[:, None]
+    side = np.where(rng.integers(0, 2, (n, 1)) == 1, 1.0, -1.0)
+    return on + side * edge * inward
+
+
+def towards(rng, points, spread=30.0, length=(0.5, 200.0), lift=60.0):
+    n = len(points)
+    o = points + rng.normal(0, spread, (n, 3)) + np.array([0, 0, lift])
+    d = points - o
+    d *= (rng.uniform(*length, n) / np.linalg.norm(d, axis=1))[:, None]
+    return o, d
+
+
+def with_misses(rng, o, d, n, centre, far=40.0):
+    """`n` more rays that pass `far` units or more from `centre`."""
+    o2, d2 = aimed(rng, n, centre, 1.0, 150.0)
+    side = np.cross(d2, rng.normal(size=(n, 3)))
+    side /= np.linalg.norm(side, axis=1)[:, None]
+    o2 = o2 + side * rng.uniform(far, 2 * far, (n, 1))
+    return np.concatenate([o, o2]), np.concatenate([d, d2])
+
+
+def build_cast_family(pkg, name):
+    rng = np.random.default_rng(sum(name.encode()))
+    if name == "base_random":
+        scene = gs.base_scene(pkg)
+        return scene, yr.random_rays(scene, 480, 21, box=((0, 96), (0, 80), (-110, 30))), "mixed"
+    if name.startswith("sphere_"):
+        distance, r = (int(v) for v in name.split("_")[1:])
+        kind = "outside" if (distance, r) in ((4096, 3), (30000, 3)) else "sphere"
+        return (*sphere_row(pkg, distance, r), kind)
+    if name == "inside_and_away":  # the far root from inside; from outside, pointing away
+        r = 30.0
+        u = rng.normal(size=(300, 3))
+        u /= np.linalg.norm(u, axis=1)[:, None]
+        inside = np.asarray(CENTRE) + u * rng.uniform(0, 0.9 * r, (300, 1))
+        v = rng.normal(size=(300, 3))
+        v *= (rng.uniform(0.5, 200.0, 300) / np.linalg.norm(v, axis=1))[:, None]
+        o, d = aimed(rng, 300, CENTRE, 0.8 * r, 100.0)
+        return one_sphere(pkg, r), rays_of(np.concatenate([inside, o]), np.concatenate([v, -d])), \
+            "sphere"
+    if name in ("two_spheres_near_first", "two_spheres_far_first"):
+        near, far = ((40, 30, -50, 1), 10, WHITE), ((40, 30, -100, 1), 10, WHITE)
+        order = [near, far] if name.endswith("near_first") else [far, near]
+        o, d = along_axis(rng, 600, (40, 30, -100), 9.0, origin_spread=25.0)
+        return gs.scene_from(pkg, spheres=order), rays_of(o, d), "sphere"
+    if name in ("cube_before_sphere", "cube_behind_sphere"):
+        zc, zs = (-40, -90) if name == "cube_before_sphere" else (-90, -40)
+        o, d = along_axis(rng, 400, (40, 30, min(zc, zs)), 9.0, origin_spread=25.0)
+        return cube_and_sphere(pkg, zc, zs), rays_of(o, d), "mixed"
+    if name == "ties":  # two equal spheres and two equal cubes, with and without the first left out
+        scene = gs.scene_from(pkg, **gs.EDGE_CASES["ties"])
+        o1, d1 = along_axis(rng, 250, (50, 40, -50), 18.0)
+        o2, d2 = along_axis(rng, 250, (20, 20, -30), 9.0)
+        skip = rng.choice([-1, -1, 0, 1, 2, 3], 500)
+        return scene, rays_of(np.concatenate([o1, o2]), np.concatenate([d1, d2]), skip), "mixed"
+    if name in ("length_1e-4", "length_1e3"):
+        scene = scaled_scene(pkg)
+        # (at |d| = 1e-4 a hit further than 30 units away is past 300000: a miss)
+        near = dict(spread=5.0, lift=14.0) if name == "length_1e-4" else {}
+        o1, d1 = towards(rng, cube_points(scene, rng, 150, 0), **near)
+        o2, d2 = towards(rng, cube_points(scene, rng, 100, 1), spread=5.0, lift=14.0)
+        o3, d3 = aimed(rng, 200, (60, 30, -40), 7.0, 22.0 if near else 90.0)
+        o, d = np.concatenate([o1, o2, o3]), np.concatenate([d1, d2, d3])
+        d *= (float(name.split("_")[1]) / np.linalg.norm(d, axis=1))[:, None]
+        return scene, rays_of(o, d), "mixed"
+    if name in ("triangle_interior", "triangle_edges"):
+        scene = gs.scene_from(pkg, cubes=[(ROTATED + [("translate", 40, 30, -40)], WHITE)])
+        edge = None if name == "triangle_interior" else 1e-3
+        o, d = towards(rng, cube_points(scene, rng, 260, 0, edge))
+        o, d = with_misses(rng, o, d, 120, (40, 30, -40))
+        return scene, rays_of(o, d), "mixed" if edge is None else "edge"
+    raise KeyError(name)
+
+
+CAST_FAMILIES = ["base_random", "sphere_50_3", "sphere_500_3", "sphere_500_30", "sphere_4096_30",
+                 "inside_and_away", "two_spheres_near_first", "two_spheres_far_first",
+                 "cube_before_sphere", "cube_behind_sphere", "ties", "length_1e-4", "length_1e3",
+                 "triangle_interior", "triangle_edges"]
+OUTSIDE_FAMILIES = ["sphere_4096_3", "sphere_30000_3"]
+CAPS = {"sphere": 0.10, "mixed": 0.01, "edge": 0.0}
+
+
+def kinds_of(geometry, obj):
+    return {"cube": int(((obj >= 0) & (obj < geometry.nc)).sum()),
+            "sphere": int((obj >= geometry.nc).sum())}
+
+
+def cast_family(pkg, name):
+    """The family with its exact answers, once per session.  On the base scene
+    a third of the rays leave out the object they would meet."""
+    if ("cast", name) in _CACHE:
+        return _CACHE["cast", name]
+    scene, rays, kind = build_cast_family(pkg, name)
+    rays = np.ascontiguousarray(rays, pkg.RAY_DTYPE).reshape(-1)
+    geometry = ex.Geometry(scene)
+    pairs = ex.Pairs(geometry, rays)
+    free = ex.closest(pairs, skip=-1)
+    if name == "base_random":
+        own = (np.arange(len(rays)) % 3 == 0) & (free.status == ex.DECIDED_HIT)
+        rays["skip"][own] = free.obj[own]
+        pairs.skip = rays["skip"].astype(np.int64)
+    ref = ex.closest(pairs)
+    f = SimpleNamespace(name=name, scene=scene, rays=rays, kind=kind, geometry=geometry,
+                        pairs=pairs, ref=ref, free=free)
+    f.hits = int((ref.status == ex.DECIDED_HIT).sum())
+    f.misses = int((ref.status == ex.DECIDED_MISS).sum())
+    f.excluded = float((ref.status == ex.UNDECIDED).mean())
+    f.skipped_own = (free.status == ex.DECIDED_HIT) & (free.obj == pairs.skip)
+    _CACHE["cast", name] = f
+    return f
+
+
+def check_cast_caps(f):
+    """On the reference alone."""
+    if f.kind == "outside":
+        band = np.abs(f.pairs.spheres[0].disc) <= f.pairs.spheres[0].E
+        assert band.mean() > 0.9, (f.name, band.mean())  # the documented limit is real
+        return
+    assert f.excluded <= CAPS[f.kind], (f.name, f.excluded)
+    assert f.hits >= 100 and f.misses >= 100, (f.name, f.hits, f.misses)
+    if f.kind == "edge":
+        # 1e-3 from an edge is far outside every band: nothing is excluded, and a hit
+        # names one of the triangles beside the edge (judge_cast's membership)
+        assert f.excluded == 0
+    if f.name == "inside_and_away":
+        assert f.ref.far.sum() >= 100
+    if f.name.startswith("two_spheres"):
+        nearer = 0 if f.name.endswith("near_first") else 1
+        won = f.ref.obj[f.ref.status == ex.DECIDED_HIT]
+        assert (won == nearer).sum() >= 100 and (won == 1 - nearer).sum() >= 10, f.name
+    if f.name in ("cube_before_sphere", "cube_behind_sphere"):
+        won = kinds_of(f.geometry, f.ref.obj[f.ref.status == ex.DECIDED_HIT])
+        assert min(won.values()) >= 10, (f.name, won)
+    if f.name == "ties":
+        won = f.ref.obj[f.ref.status == ex.DECIDED_HIT]
+        assert all((won == s).sum() >= 10 for s in range(4)), np.bincount(won)
+    if f.name == "length_1e-4":
+        # rays aimed into the small cube: the line crosses it, |det| < 1e-6 turns it off
+        small = [any(abs(tp.det) < ex.EPSILON and tp.u is not None and tp.u > 0 and tp.v > 0
+                     and tp.u + tp.v < 1 and tp.t > 0 for tp in f.pairs.tri[i][1])
+                 for i in range(f.pairs.n)]
+        assert sum(small) >= 50 and not (f.ref.obj == 1).any()
+    if f.name == "length_1e3":
+        assert (f.ref.obj[f.ref.status == ex.DECIDED_HIT] == 1).sum() >= 20
+    if f.name == "base_random":
+        assert f.skipped_own.sum() >= 50
+
+
+# ---------------------------------------------------------------------------
+# cast_rays and its two culled variants
+# ---------------------------------------------------------------------------
+def library_casts(pkg, f):
+    """(name, t, object, triangle) of cast_rays, cast_rays_accel, cast_rays_grouped."""
+    accel, groups = pkg.build_accel(f.scene), pkg.build_sphere_groups(f.scene)
+    for name, got in (("cast_rays", pkg.cast_rays(f.rays, f.scene, triangles=True)),
+                      ("cast_rays_accel", pkg.cast_rays_accel(f.rays, f.scene, accel, True)),
+                      ("cast_rays_grouped", pkg.cast_rays_grouped(f.rays, f.scene, accel, groups,
+                                                                  True))):
+        yield name, got[0]["t"], got[0]["object"], got[1]
+
+
+@pytest.mark.parametrize("name", CAST_FAMILIES)
+def test_cast_rays(pkg, name):
+    f = cast_family(pkg, name)
+    check_cast_caps(f)
+    for call, t, obj, tri in library_casts(pkg, f):
+        bad = ex.judge_cast(f.pairs, f.ref, t, obj, tri)
+        assert not bad, (call, bad)
+        rel, share = ex.t_errors(f.ref, t)
+        print(f"{name} {call}: excluded {f.excluded:.4f}, hits {f.hits}, misses {f.misses}, "
+              f"worst t error {rel:.3g} relative, {share:.3g} of the tolerance")
+        assert share <= 1.0
+
+
+@pytest.mark.parametrize("name", OUTSIDE_FAMILIES)
+def test_cast_rays_outside_the_domain(pkg, name):
+    """These rows decide almost nothing: the band holds more than 90 % of the
+    rays.  Outside the band no verdict is wrong, and no word is NaN or an id
+    outside the scene (judge_cast looks at every ray for those)."""
+    f = cast_family(pkg, name)
+    check_cast_caps(f)
+    for call, t, obj, tri in library_casts(pkg, f):
+        bad = ex.judge_cast(f.pairs, f.ref, t, obj, tri)
+        assert not bad, (call, bad)
+        sp = f.pairs.spheres[0]
+        outside = np.abs(sp.disc) > sp.E
+        assert ((obj == 0) == (sp.disc > 0))[outside & (sp.B > 0)].all(), call
+    print(f"{name}: in the band {(np.abs(sp.disc) <= sp.E).mean():.4f}, "
+          f"decided {1 - f.excluded:.4f}")
+
+
+# ---------------------------------------------------------------------------
+# occlude_rays and its two variants
+# ---------------------------------------------------------------------------
+def build_segment_family(pkg, name):
+    rng = np.random.default_rng(sum(name.encode()))
+    if name == "base_segments":
+        scene = gs.base_scene(pkg)
+        return scene, yr.random_rays(scene, 360, 22, box=((0, 96), (0, 80), (-110, 30))), "mixed"
+    if name == "ends":  # before, inside and beyond a sphere and a cube
+        scene = gs.scene_from(pkg, spheres=[((70, 30, -40, 1), 8, WHITE)],
+                              cubes=[(ROTATED + [("translate", 30, 30, -40)], WHITE)])
+        o1, d1 = aimed(rng, 300, (70, 30, -40), 3.0, 60.0)
+        o2, d2 = aimed(rng, 300, (30, 30, -40), 1.5, 60.0)
+        o, d = np.concatenate([o1, o2]), np.concatenate([d1, d2])
+        d /= np.linalg.norm(d, axis=1)[:, None]
+        # the aim point is 60 units away, inside the occluder
+        d *= rng.choice([30.0, 45.0, 60.0, 61.0, 90.0, 150.0], len(d))[:, None]
+        return scene, rays_of(o, d), "mixed"
+    if name == "inside_a_sphere":  # start inside: end inside (free) or outside (occluded)
+        r = 30.0
+        u = rng.normal(size=(500, 3))
+        u /= np.linalg.norm(u, axis=1)[:, None]
+        o = np.asarray(CENTRE) + u * rng.uniform(0, 0.6 * r, (500, 1))
+        v = rng.normal(size=(500, 3))
+        v *= (rng.choice([3.0, 9.0, 70.0, 150.0], 500) / np.linalg.norm(v, axis=1))[:, None]
+        return one_sphere(pkg, r), rays_of(o, v), "sphere"
+    if name == "behind_the_origin":
+        scene = cube_and_sphere(pkg, -40, -90)
+        o, d = along_axis(rng, 500, (40, 30, -65), 9.0)
+        d *= (200.0 / np.linalg.norm(d, axis=1))[:, None]
+        d[::2] *= -1  # half of them look away from both
+        return scene, rays_of(o, d), "mixed"
+    if name in ("skip_the_only_sphere", "skip_the_only_cube"):
+        if name.endswith("sphere"):
+            scene = one_sphere(pkg, 8.0, (40, 30, -40))
+        else:
+            scene = gs.scene_from(pkg, cubes=[(ROTATED + [("translate", 40, 30, -40)], WHITE)])
+        o, d = aimed(rng, 500, (40, 30, -40), 2.0, 60.0)
+        d *= (150.0 / np.linalg.norm(d, axis=1))[:, None]
+        return scene, rays_of(o, d, np.where(np.arange(500) % 2 == 0, 0, -1)), \
+            "sphere" if name.endswith("sphere") else "mixed"
+    raise KeyError(name)
+
+
+SEGMENT_FAMILIES = ["base_segments", "ends", "inside_a_sphere", "behind_the_origin",
+                    "skip_the_only_sphere", "skip_the_only_cube"]
+
+
+def segment_family(pkg, name):
+    if ("segment", name) in _CACHE:
+        return _CACHE["segment", name]
+    scene, rays, kind = build_segment_family(pkg, name)
+    rays = np.ascontiguousarray(rays, pkg.RAY_DTYPE).reshape(-1)
+    geometry = ex.Geometry(scene)
+    pairs = ex.Pairs(geometry, rays)
+    ref, free = ex.occlusion(pairs), ex.occlusion(pairs, skip=-1)
+    f = SimpleNamespace(name=name, scene=scene, rays=rays, kind=kind, geometry=geometry,
+                        pairs=pairs, ref=ref, free=free)
+    f.hits = int((ref.status == ex.DECIDED_HIT).sum())
+    f.misses = int((ref.status == ex.DECIDED_MISS).sum())
+    f.excluded = float((ref.status == ex.UNDECIDED).mean())
+    # the own object, left out, was the only occluder
+    f.skipped_own = (free.status == ex.DECIDED_HIT) & (ref.status == ex.DECIDED_MISS)
+    _CACHE["segment", name] = f
+    return f
+
+
+def check_segment_caps(f):
+    assert f.excluded <= CAPS[f.kind], (f.name, f.excluded)
+    assert f.hits >= 100 and f.misses >= 100, (f.name, f.hits, f.misses)
+    if f.name.startswith("skip_the_only"):
+        skipped = f.pairs.skip == 0
+        assert (f.ref.status[skipped] == ex.DECIDED_MISS).all() and f.skipped_own.sum() >= 100
+    if f.name == "behind_the_origin":
+        assert (f.ref.status[::2] == ex.DECIDED_MISS).all()
+    if f.name == "inside_a_sphere":
+        s = f.pairs.spheres[0]
+        both_inside = (s.s0 < 0) & (s.s1 > 1)  # no root in (0, 1): not occluded
+        assert (both_inside & (f.ref.status == ex.DECIDED_MISS)).sum() >= 100
+    if f.name == "ends":
+        assert f.ref.by_cube.sum() >= 50 and f.ref.by_sphere.sum() >= 50
+
+
+@pytest.mark.parametrize("name", SEGMENT_FAMILIES)
+def test_occlude_rays(pkg, name):
+    f = segment_family(pkg, name)
+    check_segment_caps(f)
+    accel, groups = pkg.build_accel(f.scene), pkg.build_sphere_groups(f.scene)
+    for call, got in (("occlude_rays", pkg.occlude_rays(f.rays, f.scene)),
+                      ("occlude_rays_accel", pkg.occlude_rays_accel(f.rays, f.scene, accel)),
+                      ("occlude_rays_grouped",
+                       pkg.occlude_rays_grouped(f.rays, f.scene, accel, groups))):
+        bad = ex.judge_occlude(f.ref, got)
+        assert not bad, (call, bad)
+    print(f"{name}: excluded {f.excluded:.4f}, occluded {f.hits}, free {f.misses}")
+
+
+# ---------------------------------------------------------------------------
+# Frames: hit_surfaces, shadow_hits, bounce_hits (bounce 1)
+# ---------------------------------------------------------------------------
+def frame_rays(d, w=FW, h=FH):
+    ys, xs = np.mgrid[0:h, 0:w]
+    return yr.make_rays((xs, ys, 0.0), d[:3], -1).reshape(-1)
+
+
+def frame(pkg, which, d):
+    """The rays of Camera.reference(d) over 37 x 29 on `which` scene, with
+    their exact closest hits."""
+    key = ("frame", which, tuple(d))
+    if key not in _CACHE:
+        scene = {"frame": frame_scene, "shadow": shadow_scene,
+                 "mirror": flat_mirror_scene}[which](pkg)
+        rays = np.ascontiguousarray(frame_rays(d), pkg.RAY_DTYPE)
+        geometry = ex.Geometry(scene)
+        pairs = ex.Pairs(geometry, rays)
+        f = SimpleNamespace(scene=scene, rays=rays, d=d, geometry=geometry, pairs=pairs,
+                            ref=ex.closest(pairs), kind="mixed", name=which)
+        f.excluded = float((f.ref.status == ex.UNDECIDED).mean())
+        f.hits = int((f.ref.status == ex.DECIDED_HIT).sum())
+        f.misses = int((f.ref.status == ex.DECIDED_MISS).sum())
+        _CACHE[key] = f
+    return _CACHE[key]
+
+
+def hit_points32(f, t):
+    """fl(o + fl(t * d)) per component, the hit point as DESIGN.md §3.1a states
+    it; (n, 3) float32.  Computed here from the library's t: the library does
+    not return its point, so this is the test's own evaluation of that formula."""
+    o, d, _ = ex.ray_arrays(f.rays)
+    return (o.astype(F32) + (np.asarray(t, F32)[:, None] * d.astype(F32))).astype(F32)
+
+
+def exact_surfaces(f):
+    """Per decided hit pixel: the exact faced unit normal, the cosine between
+    the unfaced normal and the ray, the bound of the angle between the library's
+    normal and the exact one, and the bound of the hit point's displacement."""
+    if hasattr(f, "normal"):
+        return
+    g, ref = f.geometry, f.ref
+    o, d, _ = ex.ray_arrays(f.rays)
+    o, d = o.astype(np.float64), d.astype(np.float64)
+    n = len(o)
+    f.normal, f.cos, f.angle, f.moved = np.zeros((n, 3)), np.zeros(n), np.zeros(n), np.zeros(n)
+    f.point = o + ref.t[:, None] * d
+    length = np.linalg.norm(d, axis=1)
+    for i in np.nonzero(ref.status == ex.DECIDED_HIT)[0]:
+        obj = int(ref.obj[i])
+        # t's tolerance along d, and the two roundings of o + t * d per component
+        f.moved[i] = ref.tol[i] * length[i] + 2 * U * (np.linalg.norm(o[i]) +
+                                                       2 * abs(ref.t[i]) * length[i])
+        if obj < g.nc:
+            k = min(k for k, tk, tolk in ref.tris[i][obj]
+                    if abs(tk - ref.t[i]) <= tolk + ref.tol[i])
+            normal, sin = ex.tri_normal(*g.tris[obj, k])
+            # fp32 edges (u each), cross product (3u of |e1||e2| per component), normalise
+            f.angle[i] = 16 * U / sin
+        else:
+            c, r = g.centres[obj - g.nc].astype(np.float64), float(g.radius[obj - g.nc])
+            normal = ex.sphere_normal(f.point[i], c)
+            # the displaced point seen from the centre, the subtraction, normalise
+            f.angle[i] = 1.01 * f.moved[i] / r + 8 * U
+        f.normal[i], f.cos[i] = ex.faced(normal, d[i])
+
+
+def judge_surfaces(f, hits, surf, limit=5):
+    """Violations of a surface frame `surf` of the hit frame `hits` (flat)."""
+    exact_surfaces(f)
+    bad = []
+    _, d, _ = ex.ray_arrays(f.rays)
+    d = d.astype(np.float64)
+    n_lib = np.stack([surf["nx"], surf["ny"], surf["nz"]], -1).astype(np.float64)
+    # n . d as DESIGN.md §3.1a states the facing: float32, (x + y) + z.  A normal that
+    # was turned on that sum gives exactly its negative, so <= 0 holds without a tolerance
+    d32 = d.astype(F32)
+    facing = (surf["nx"] * d32[:, 0] + surf["ny"] * d32[:, 1]) + surf["nz"] * d32[:, 2]
+    for i in range(len(hits)):
+        why = None
+        if hits["object"][i] < 0:
+            if n_lib[i].any() or surf["triangle"][i] != -1:
+                why = "a miss has no surface"
+        elif abs(np.linalg.norm(n_lib[i]) - 1) > 4 * U:
+            why = f"|n| = {np.linalg.norm(n_lib[i])!r}"
+        elif facing[i] > 0:
+            why = f"n . d = {facing[i]!r} > 0"
+        elif f.ref.status[i] == ex.DECIDED_HIT and hits["object"][i] == f.ref.obj[i]:
+            obj = int(f.ref.obj[i])
+            if obj < f.geometry.nc:
+                near = [k for k, tk, tolk in f.ref.tris[i][obj]
+                        if abs(tk - f.ref.t[i]) <= tolk + f.ref.tol[i]]
+                if surf["triangle"][i] not in near:
+                    why = f"triangle {surf['triangle'][i]}, exact: one of {near}"
+                elif len(near) > 1:
+                    continue  # on an edge: either face's normal
+            if why is None and abs(f.cos[i]) > f.angle[i] + 4 * U:
+                a = float(ex.angle(n_lib[i], f.normal[i]))
+                if a > f.angle[i]:
+                    why = f"{a:.3g} rad from the exact normal, bound {f.angle[i]:.3g}"
+        if why:
+            bad.append(f"pixel {i}: {why}")
+            if len(bad) >= limit:
+                break
+    return bad
+
+
+def check_frame_caps(f):
+    assert f.excluded <= CAPS["mixed"], f.excluded
+    assert f.hits >= 100 and f.misses >= 100, (f.hits, f.misses)
+
+
+@pytest.mark.parametrize("direction", list(FRAME_DIRS))
+def test_hit_surfaces(pkg, direction):
+    d = FRAME_DIRS[direction]
+    f = frame(pkg, "frame", d)
+    check_frame_caps(f)
+    exact_surfaces(f)
+    on = f.ref.status == ex.DECIDED_HIT
+    won = kinds_of(f.geometry, f.ref.obj[on])
+    assert min(won.values()) >= 100 and (f.ref.far & on).sum() >= 30, won
+    assert ((f.cos > 0) & on).sum() >= 30  # normals that have to be turned
+    hits, tri = pkg.cast_camera(pkg.Camera.reference(d), f.scene, FW, FH, triangles=True)
+    bad = ex.judge_cast(f.pairs, f.ref, hits["t"].ravel(), hits["object"].ravel(), tri.ravel())
+    assert not bad, bad
+    # the float32 hit point lies where t's tolerance puts it
+    moved = np.linalg.norm(hit_points32(f, hits["t"].ravel()).astype(np.float64) - f.point, axis=1)
+    assert (moved[on] <= f.moved[on]).all(), (moved[on] / f.moved[on]).max()
+    surf = pkg.hit_surfaces(hits, f.scene, ray_dir=d)
+    bad = judge_surfaces(f, hits.ravel(), surf.ravel())
+    assert not bad, bad
+    print(f"{direction}: excluded {f.excluded:.4f}, worst displacement "
+          f"{(moved[on] / f.moved[on]).max():.3g} of its bound")
+
+
+def shadow_segments(pkg, f, hits, light):
+    """The segments of light `light` from every decided hit pixel: (pixels,
+    rays (p, L, skip = object), exact cosine, its rounding)."""
+    exact_surfaces(f)
+    at = np.nonzero((f.ref.status == ex.DECIDED_HIT) & (hits["object"] == f.ref.obj))[0]
+    p = hit_points32(f, hits["t"])[at]
+    L = (np.asarray(f.scene.lights, F32).reshape(-1, 4)[light, :3][None, :] - p).astype(F32)
+    rays = np.ascontiguousarray(rays_of(p, L, hits["object"][at]), pkg.RAY_DTYPE)
+    cos = (f.normal[at] * ex.unit(L.astype(np.float64))).sum(-1)
+    return at, rays, cos, f.angle[at] + 8 * U
+
+
+def shadow_reference(pkg, f, hits, light):
+    key = ("shadow", f.name, tuple(f.d), light)
+    if key not in _CACHE:
+        at, rays, cos, rounding = shadow_segments(pkg, f, hits, light)
+        pairs = ex.Pairs(f.geometry, rays)
+        occ = ex.occlusion(pairs)
+        clear = np.abs(cos) > rounding
+        # the bit: 1, 0, or -1 where the cosine or the segment is not decided
+        want = np.where(~clear | ((cos > 0) & (occ.status == ex.UNDECIDED)), -1,
+                        np.where((cos > 0) & (occ.status == ex.DECIDED_HIT), 1, 0))
+        _CACHE[key] = SimpleNamespace(at=at, want=want, occ=occ, cos=cos, rays=rays)
+    return _CACHE[key]
+
+
+def judge_shadow(refs, mask):
+    bad = []
+    for light, r in enumerate(refs):
+        bit = (mask[r.at] >> light) & 1
+        wrong = (r.want >= 0) & (bit != r.want)
+        bad += [f"light {light} pixel {r.at[i]}: bit {bit[i]}, exact {r.want[i]}"
+                for i in np.nonzero(wrong)[0][:3]]
+    if (mask >> len(refs)).any():
+        bad.append("a bit of a light the scene does not have")
+    return bad
+
+
+def shadow_case(pkg):
+    f = frame(pkg, "shadow", FRAME_DIRS["reference"])
+    assert f.excluded <= CAPS["mixed"] and f.hits >= 1000  # (the slab fills the frame)
+    hits, tri = pkg.cast_camera(pkg.Camera.reference(f.d), f.scene, FW, FH, triangles=True)
+    # the frame whose t the segments start from is itself judged
+    bad = ex.judge_cast(f.pairs, f.ref, hits["t"].ravel(), hits["object"].ravel(), tri.ravel())
+    assert not bad, bad
+    refs = [shadow_reference(pkg, f, hits.ravel(), light) for light in range(2)]
+    for r in refs:  # on the reference alone: per light, as every family
+        occluded, free = r.want == 1, (r.want == 0) & (r.cos > 0)
+        assert occluded.sum() >= 100 and free.sum() >= 100, (occluded.sum(), free.sum())
+        assert (r.want == -1).mean() <= CAPS["mixed"]
+        assert r.occ.by_cube[occluded].sum() >= 30 and r.occ.by_sphere[occluded].sum() >= 30
+    assert sum(((r.cos < 0) & (r.want == 0)).sum() for r in refs) >= 20  # lights behind the surface
+    return f, hits, refs
+
+
+def test_shadow_hits(pkg):
+    f, hits, refs = shadow_case(pkg)
+    bad = judge_shadow(refs, pkg.shadow_hits(hits, f.scene, ray_dir=f.d).ravel())
+    assert not bad, bad
+    accel = pkg.build_accel(f.scene)
+    bad = judge_shadow(refs, pkg.shadow_hits_accel(hits, f.scene, accel, ray_dir=f.d).ravel())
+    assert not bad, bad
+
+
+def bounce_case(pkg):
+    """The first bounce on the flat mirror: the exact normal of the slab's
+    front face is (0, 0, 1) and the mirrored direction (d.x, d.y, -d.z), both
+    exact in float32, so the library casts exactly (p, R) from its float32 hit
+    point p, which is taken as an exact real here."""
+    f = frame(pkg, "mirror", MIRROR_DIR)
+    key = ("bounce", "mirror")
+    hits, tri = pkg.cast_camera(pkg.Camera.reference(f.d), f.scene, FW, FH, triangles=True)
+    # the mirror frame, whose t the bounce starts from, is itself judged
+    bad = ex.judge_cast(f.pairs, f.ref, hits["t"].ravel(), hits["object"].ravel(), tri.ravel())
+    assert not bad, bad
+    if key not in _CACHE:
+        exact_surfaces(f)
+        flat = hits.ravel()
+        at = np.nonzero((f.ref.status == ex.DECIDED_HIT) & (f.ref.obj == 0) &
+                        (flat["object"] == 0))[0]
+        assert len(at) == FW * FH and (f.normal[at] == (0.0, 0.0, 1.0)).all()
+        R = ex.mirror(f.normal[at], np.asarray(f.d[:3], np.float64))
+        assert (R == (f.d[0], f.d[1], -f.d[2])).all() and (R.astype(F32) == R).all()
+        at = at[::2]
+        rays = np.ascontiguousarray(rays_of(hit_points32(f, flat["t"])[at], R[::2], 0),
+                                    pkg.RAY_DTYPE)
+        pairs = ex.Pairs(f.geometry, rays)
+        b = SimpleNamespace(at=at, rays=rays, pairs=pairs, ref=ex.closest(pairs))
+        b.excluded = float((b.ref.status == ex.UNDECIDED).mean())
+        _CACHE[key] = b
+    b = _CACHE[key]
+    won = kinds_of(f.geometry, b.ref.obj[b.ref.status == ex.DECIDED_HIT])
+    assert b.excluded <= CAPS["mixed"] and min(won.values()) >= 30, (b.excluded, won)
+    assert sum(won.values()) >= 100 and (b.ref.status == ex.DECIDED_MISS).sum() >= 100
+    return f, hits, b
+
+
+def test_bounce_hits_first_bounce(pkg):
+    f, hits, b = bounce_case(pkg)
+    accel = pkg.build_accel(f.scene)
+    for call, got in (("bounce_hits", pkg.bounce_hits(hits, f.scene, 1, ray_dir=f.d)),
+                      ("bounce_hits_accel",
+                       pkg.bounce_hits_accel(hits, f.scene, accel, 1, ray_dir=f.d)),
+                      ("reflect_hits", pkg.reflect_hits(hits, f.scene, ray_dir=f.d))):
+        got = got.ravel()[b.at]
+        bad = ex.judge_cast(b.pairs, b.ref, got["t"], got["object"])
+        assert not bad, (call, bad)
+
+
+# ---------------------------------------------------------------------------
+# Every object kind wins, occludes and is left out
+# ---------------------------------------------------------------------------
+def test_every_kind_everywhere(pkg):
+    winners, occluders = {"cube": 0, "sphere": 0}, {"cube": 0, "sphere": 0}
+    own_cast, own_segment = {"cube": 0, "sphere": 0}, {"cube": 0, "sphere": 0}
+    for name in CAST_FAMILIES:
+        f = cast_family(pkg, name)
+        for k, v in kinds_of(f.geometry, f.ref.obj[f.ref.status == ex.DECIDED_HIT]).items():
+            winners[k] += v
+        for k, v in kinds_of(f.geometry, f.pairs.skip[f.skipped_own]).items():
+            own_cast[k] += v
+    for name in SEGMENT_FAMILIES:
+        f = segment_family(pkg, name)
+        occluders["cube"] += int(f.ref.by_cube.sum())
+        occluders["sphere"] += int(f.ref.by_sphere.sum())
+        for k, v in kinds_of(f.geometry, f.pairs.skip[f.skipped_own]).items():
+            own_segment[k] += v
+    for counts in (winners, occluders, own_cast, own_segment):
+        assert min(counts.values()) >= 20, (winners, occluders, own_cast, own_segment)
+
+
+# ---------------------------------------------------------------------------
+# The families can tell: deliberately wrong variants of a plain float64 walk
+# (test code; nothing is patched into the library)
+# ---------------------------------------------------------------------------
+VARIANTS = ["far_root", "last_minimum", "r_for_r_squared", "segment_to_infinity", "skip_ignored",
+            "normal_not_turned", "no_u_plus_v", "last_triangle_tested"]
+
+
+def plain_triangle(o, d, tri, variant):
+    """Moeller-Trumbore in float64 over n rays: (candidate, t)."""
+    v0, v1, v2 = (tri[i].astype(np.float64) for i in range(3))
+    e1, e2 = v1 - v0, v2 - v0
+    with np.errstate(all="ignore"):
+        pv = np.cross(d, e2)
+        det = pv @ e1
+        tv = o - v0
+        u = (tv * pv).sum(-1) / det
+        qv = np.cross(tv, e1)
+        v = (d * qv).sum(-1) / det
+        t = (qv @ e2) / det
+        ok = (np.abs(det) >= 1e-6) & (u >= 0) & (u <= 1) & (v >= 0)
+        if variant != "no_u_plus_v":
+            ok &= u + v <= 1
+    return ok, t
+
+
+def plain_sphere(o, d, centre, r, variant):
+    """(s0, s1) of |o + s d - c| = r, NaN where the line misses."""
+    m = centre.astype(np.float64) - o
+    with np.errstate(all="ignore"):
+        a, b = (d * d).sum(-1), (m * d).sum(-1)
+        q = (m * m).sum(-1) - (float(r) if variant == "r_for_r_squared" else float(r) * float(r))
+        sq = np.sqrt(b * b - a * q)
+        return (b - sq) / a, (b + sq) / a
+
+
+def plain_cast(g, rays, variant=None):
+    o, d, skip = ex.ray_arrays(rays)
+    o, d = o.astype(np.float64), d.astype(np.float64)
+    if variant == "skip_ignored":
+        skip = np.full(len(o), -1)
+    n = len(o)
+    best, obj, tri = np.full(n, ex.K_FAR), np.full(n, -1), np.full(n, -1)
+    last = np.full(n, -1)
+    beats = (lambda t, b: t <= b) if variant == "last_minimum" else (lambda t, b: t < b)
+    with np.errstate(all="ignore"):
+        for j in range(g.nc):
+            for k in range(12):
+                ok, t = plain_triangle(o, d, g.tris[j, k], variant)
+                ok &= (t > 0) & (skip != j)
+                last[ok] = k
+                take = ok & beats(t, best)
+                best[take], obj[take], tri[take] = t[take], j, k
+        for s in range(g.ns):
+            s0, s1 = plain_sphere(o, d, g.centres[s], g.radius[s], variant)
+            if variant == "far_root":
+                sf = np.where(s1 > 0, s1, np.nan)
+            else:
+                sf = np.where(s0 > 0, s0, np.where(s1 > 0, s1, np.nan))
+            take = (skip != g.nc + s) & beats(sf, best)
+            best[take], obj[take], tri[take] = sf[take], g.nc + s, -1
+    if variant == "last_triangle_tested":
+        tri = np.where(tri >= 0, last, tri)
+    return best, obj, tri
+
+
+def plain_occlude(g, rays, variant=None):
+    o, d, skip = ex.ray_arrays(rays)
+    o, d = o.astype(np.float64), d.astype(np.float64)
+    if variant == "skip_ignored":
+        skip = np.full(len(o), -1)
+    end = np.inf if variant == "segment_to_infinity" else 1.0
+    flags = np.zeros(len(o), bool)
+    with np.errstate(all="ignore"):
+        for j in range(g.nc):
+            for k in range(12):
+                ok, t = plain_triangle(o, d, g.tris[j, k], variant)
+                flags |= ok & (t > 0) & (t < end) & (skip != j)
+        for s in range(g.ns):
+            s0, s1 = plain_sphere(o, d, g.centres[s], g.radius[s], variant)
+            flags |= (skip != g.nc + s) & (((s0 > 0) & (s0 < end)) | ((s1 > 0) & (s1 < end)))
+    return flags.astype(np.uint8)
+
+
+def plain_surfaces(pkg, f, t, obj, tri, variant=None):
+    o, d, _ = ex.ray_arrays(f.rays)
+    o, d = o.astype(np.float64), d.astype(np.float64)
+    surf = np.zeros(len(o), pkg.SURFACE_DTYPE)
+    surf["triangle"] = tri
+    g = f.geometry
+    for i in np.nonzero(obj >= 0)[0]:
+        if obj[i] < g.nc:
+            v0, v1, v2 = g.tris[obj[i], tri[i]].astype(np.float64)
+            n = ex.unit(np.cross(v1 - v0, v2 - v0))
+        else:
+            n = ex.unit(o[i] + t[i] * d[i] - g.centres[obj[i] - g.nc])
+        # (turned on the float32 words it returns, as the judge reads them)
+        n, d32 = n.astype(F32), d[i].astype(F32)
+        if variant != "normal_not_turned" and (n[0] * d32[0] + n[1] * d32[1]) + n[2] * d32[2] > 0:
+            n = -n
+        surf["nx"][i], surf["ny"][i], surf["nz"][i] = n
+    return surf
+
+
+def rejected_by(pkg, variant):
+    """The first family that rejects the plain walk's `variant` (None: none)."""
+    for name in CAST_FAMILIES:
+        f = cast_family(pkg, name)
+        if ex.judge_cast(f.pairs, f.ref, *plain_cast(f.geometry, f.rays, variant)):
+            return "cast " + name
+    for name in SEGMENT_FAMILIES:
+        f = segment_family(pkg, name)
+        if ex.judge_occlude(f.ref, plain_occlude(f.geometry, f.rays, variant)):
+            return "segments " + name
+    for direction, d in FRAME_DIRS.items():
+        f = frame(pkg, "frame", d)
+        t, obj, tri = plain_cast(f.geometry, f.rays, variant)
+        hits = np.zeros(len(t), pkg.HIT_DTYPE)
+        hits["t"], hits["object"] = t, obj
+        if judge_surfaces(f, hits, plain_surfaces(pkg, f, t, obj, tri, variant)):
+            return "surfaces " + direction
+    return None
+
+
+def test_the_plain_walk_passes(pkg):
+    """The checker is not so strict that a correct float64 walk fails it."""
+    assert rejected_by(pkg, None) is None
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_a_wrong_walk_is_rejected(pkg, variant):
+    where = rejected_by(pkg, variant)
+    print(f"{variant}: rejected by {where}")
+    assert where is not None, f"no family rejects {variant}: a family is missing"
