@@ -1,9 +1,10 @@
 /*
  * rt_accel_impl.h -- the cube cull of the ray queries, rt_accel_build* and
  * rt_cast_rays_accel* / rt_occlude_rays_accel* / rt_cast_camera_accel*
- * (DESIGN.md §3.1g): the record of one cube, the keep test and the scalar
- * culled walks, one text for the host functions (csrc/rt_accel.cpp) and the
- * kernels (csrc/rt_accel.hip), and their shared argument checks.  The exact
+ * (DESIGN.md §3.1g): the record of one cube, the keep test and the cull policy
+ * that puts it into the walks of rt_light_impl.h, one text for the host
+ * functions (csrc/rt_accel.cpp) and the kernels (csrc/rt_accel.hip and the
+ * culled light pass), and their shared argument checks.  The exact
  * tests are rt_light_impl.h's bounce_tri, occluded_by_tri and the sphere tests,
  * as they are.  Internal: not installed, not part of the ABI.
  *
@@ -201,61 +202,21 @@ RT_LIGHT_FN bool cube_kept(const double* o, const double* d, const rt_cube_bound
     return !slab_misses(o, d, b, load / g + slack, segment);
 }
 
-// bounce_walk with the cubes the keep test drops left out: the same order,
-// the same rule, the unculled sphere loop.
-RT_LIGHT_FN Bounce bounce_walk_culled(const rt_scene& s, const rt_cube_bound* accel, int32_t obj,
-                                      Vec3 p, Vec3 R) {
-    Bounce b{kFar, -1, -1};
-    const double pd[3] = {p.x, p.y, p.z};
-    const double Rd[3] = {R.x, R.y, R.z};
-    float sf;
-    for (int32_t j = 0; j < s.num_cubes; ++j) {
-        if (j == obj || !cube_kept(pd, Rd, accel[j], false)) continue;
-        const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
-        for (int k = 0; k < 12; ++k)
-            if (bounce_tri(pd, Rd, v + 12 * k, &sf) && sf < b.best) b = Bounce{sf, j, k};
-    }
-    for (int32_t i = 0; i < s.num_spheres; ++i) {
-        if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
-        if (bounce_sphere(p, R, s.sphere_origins + 4 * static_cast<int64_t>(i),
-                          s.sphere_radius[i], &sf) &&
-            sf < b.best)
-            b = Bounce{sf, s.num_cubes + i, -1};
-    }
-    return b;
-}
-
-// light_occluded with the cubes the keep test drops left out.
-RT_LIGHT_FN bool light_occluded_culled(const rt_scene& s, const rt_cube_bound* accel, int32_t obj,
-                                       Vec3 p, Vec3 L) {
-    const double pd[3] = {p.x, p.y, p.z};
-    const double Ld[3] = {L.x, L.y, L.z};
-    for (int32_t j = 0; j < s.num_cubes; ++j) {
-        if (j == obj || !cube_kept(pd, Ld, accel[j], true)) continue;
-        const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
-        for (int k = 0; k < 12; ++k)
-            if (occluded_by_tri(pd, Ld, v + 12 * k)) return true;
-    }
-    for (int32_t i = 0; i < s.num_spheres; ++i) {
-        if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
-        if (occluded_by_sphere(p, L, s.sphere_origins + 4 * static_cast<int64_t>(i),
-                               s.sphere_radius[i]))
-            return true;
-    }
-    return false;
-}
-
-// rt_light_impl.h's Walks over the two culled walks: what the pixel functions
-// of the *_accel light pass take.
-struct CulledWalks {
+// The cull policy of rt_light_impl.h's walks over the prebuilt records: a cube
+// the keep test drops is left out; the same order, the same rule, the unculled
+// sphere loop.
+struct CubeCull {
+    static constexpr bool kGroups = false;
     const rt_cube_bound* accel;
-    RT_LIGHT_FN bool occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L) const {
-        return light_occluded_culled(s, accel, obj, p, L);
-    }
-    RT_LIGHT_FN Bounce bounce(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R) const {
-        return bounce_walk_culled(s, accel, obj, p, R);
+    RT_LIGHT_FN bool cube(const double* o, const double* d, int32_t j, bool segment) const {
+        return cube_kept(o, d, accel[j], segment);
     }
 };
+RT_LIGHT_FN CubeCull cull_of(const rt_cube_bound* accel) { return CubeCull{accel}; }
+
+// rt_light_impl.h's Walks over the two culled walks: what the pixel functions
+// of the *_accel light pass take.  CulledWalks{accel}.
+using CulledWalks = WalksOver<CubeCull>;
 
 }  // namespace rt_light
 

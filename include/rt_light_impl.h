@@ -243,24 +243,43 @@ RT_LIGHT_FN bool occluded_by_sphere(Vec3 p, Vec3 L, const float* centre, float r
     return (s0 > 0.0f && s0 < 1.0f) || (s1 > 0.0f && s1 < 1.0f);
 }
 
+// The cull policy of a walk: cube(o, d, j, segment) says whether the ray
+// (o, d: the doubles of its floats; segment: the shadow walk's (0, 1), else the
+// bounce's (0, inf)) has to test cube j.  A policy with kGroups also walks the
+// spheres itself (rt_sphere_groups_impl.h); the others leave them to the walk's
+// own loop.  This one keeps every cube: the unculled walks.  The wave's walks of
+// csrc/rt_light_device.inc take the same policies.
+struct KeepAll {
+    static constexpr bool kGroups = false;
+    RT_LIGHT_FN bool cube(const double*, const double*, int32_t, bool) const { return true; }
+};
+// The policy of a ray-query kernel's cull arguments (csrc/rt_rays_device.inc): none.
+RT_LIGHT_FN KeepAll cull_of() { return KeepAll{}; }
+
 // Does any object but `obj` (range-checked: a colour slot of `s`) occlude
 // the light at p + L?  The loops index 0 .. count-1 only; `obj` is compared.
-RT_LIGHT_FN bool light_occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L) {
+template <typename Cull = KeepAll>
+RT_LIGHT_FN bool light_occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L,
+                                const Cull& cull = Cull()) {
     const double pd[3] = {p.x, p.y, p.z};
     const double Ld[3] = {L.x, L.y, L.z};
     for (int32_t j = 0; j < s.num_cubes; ++j) {
-        if (j == obj) continue;
+        if (j == obj || !cull.cube(pd, Ld, j, true)) continue;
         const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
         for (int k = 0; k < 12; ++k)
             if (occluded_by_tri(pd, Ld, v + 12 * k)) return true;
     }
-    for (int32_t i = 0; i < s.num_spheres; ++i) {
-        if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
-        if (occluded_by_sphere(p, L, s.sphere_origins + 4 * static_cast<int64_t>(i),
-                               s.sphere_radius[i]))
-            return true;
+    if constexpr (Cull::kGroups) {
+        return cull.occluded_by_spheres(s, pd, Ld, obj, p, L);
+    } else {
+        for (int32_t i = 0; i < s.num_spheres; ++i) {
+            if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
+            if (occluded_by_sphere(p, L, s.sphere_origins + 4 * static_cast<int64_t>(i),
+                                   s.sphere_radius[i]))
+                return true;
+        }
+        return false;
     }
-    return false;
 }
 
 // The two walks of a pixel function, as one value: light_occluded and
@@ -395,36 +414,47 @@ struct Bounce {
 // colour slot of `s`; compared, never an index): cubes 0 .. nc-1 with
 // triangles 0 .. 11, then spheres 0 .. ns-1.  A candidate is taken iff
 // sf < best, so ties go to the first in that order (the reference's rule).
-RT_LIGHT_FN Bounce bounce_walk(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R) {
+// A cull policy leaves out cubes (and groups of spheres) it proves missed.
+template <typename Cull = KeepAll>
+RT_LIGHT_FN Bounce bounce_walk(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R,
+                               const Cull& cull = Cull()) {
     Bounce b{kFar, -1, -1};
     const double pd[3] = {p.x, p.y, p.z};
     const double Rd[3] = {R.x, R.y, R.z};
     float sf;
     for (int32_t j = 0; j < s.num_cubes; ++j) {
-        if (j == obj) continue;
+        if (j == obj || !cull.cube(pd, Rd, j, false)) continue;
         const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
         for (int k = 0; k < 12; ++k)
             if (bounce_tri(pd, Rd, v + 12 * k, &sf) && sf < b.best) b = Bounce{sf, j, k};
     }
-    for (int32_t i = 0; i < s.num_spheres; ++i) {
-        if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
-        if (bounce_sphere(p, R, s.sphere_origins + 4 * static_cast<int64_t>(i),
-                          s.sphere_radius[i], &sf) &&
-            sf < b.best)
-            b = Bounce{sf, s.num_cubes + i, -1};
+    if constexpr (Cull::kGroups) {
+        return cull.bounce_spheres(s, pd, Rd, obj, p, R, b);
+    } else {
+        for (int32_t i = 0; i < s.num_spheres; ++i) {
+            if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
+            if (bounce_sphere(p, R, s.sphere_origins + 4 * static_cast<int64_t>(i),
+                              s.sphere_radius[i], &sf) &&
+                sf < b.best)
+                b = Bounce{sf, s.num_cubes + i, -1};
+        }
+        return b;
     }
-    return b;
 }
 
-// The unculled pair of walks (declared in front of shadow_mask above).
-struct Walks {
+// A pair of walks over one cull policy.
+template <typename Cull>
+struct WalksOver {
+    Cull cull;
     RT_LIGHT_FN bool occluded(const rt_scene& s, int32_t obj, Vec3 p, Vec3 L) const {
-        return light_occluded(s, obj, p, L);
+        return light_occluded(s, obj, p, L, cull);
     }
     RT_LIGHT_FN Bounce bounce(const rt_scene& s, int32_t obj, Vec3 p, Vec3 R) const {
-        return bounce_walk(s, obj, p, R);
+        return bounce_walk(s, obj, p, R, cull);
     }
 };
+// The unculled pair (declared in front of shadow_mask above).
+struct Walks : WalksOver<KeepAll> {};
 
 // The unit normal at the bounce's hit point p2, turned against R.  `obj2` is
 // a colour slot of `s` and `tri2` a triangle of that cube (bounce_walk's).

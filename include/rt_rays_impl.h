@@ -29,6 +29,11 @@ int check_camera(const rt_camera* camera, const rt_scene* scene, bool with_scene
                  int32_t row_begin, int32_t row_end, const void* out, uintptr_t out_align,
                  const int32_t* triangle);
 
+// Is `p` off a multiple of `align` bytes?  (NULL is not.)
+inline bool misaligned(const void* p, uintptr_t align) {
+    return reinterpret_cast<uintptr_t>(p) % align != 0;
+}
+
 // One launch's grid: 2^31 - 1 workgroups of 256 rays.
 constexpr int64_t kMaxRays = static_cast<int64_t>(INT32_MAX) * 256;
 

@@ -2,9 +2,10 @@
  * rt_sphere_groups_impl.h -- the sphere cull of the ray queries,
  * rt_sphere_groups_build* and rt_cast_rays_grouped* / rt_occlude_rays_grouped* /
  * rt_cast_camera_grouped* (DESIGN.md §3.1j): the key, the order and the record
- * of a group of nearby spheres, the keep test and the scalar grouped walks, one
- * text for the host functions (csrc/rt_sphere_groups.cpp) and the kernels
- * (csrc/rt_sphere_groups.hip), and their shared argument checks.  The cube
+ * of a group of nearby spheres, the keep test and the host's cull policy that
+ * puts it into the walks of rt_light_impl.h, one text for the host functions
+ * (csrc/rt_sphere_groups.cpp) and the kernels (csrc/rt_sphere_groups.hip, whose
+ * policy has the wave's group loop), and their shared argument checks.  The cube
  * phase is rt_accel_impl.h's, the exact sphere tests are rt_light_impl.h's
  * bounce_sphere and occluded_by_sphere, as they are.  Internal: not installed,
  * not part of the ABI.
@@ -258,63 +259,57 @@ RT_LIGHT_FN bool sphere_takes(const Bounce& b, float sf, int32_t id, int32_t num
     return sf < b.best || (sf == b.best && b.obj2 >= num_cubes && b.obj2 > id);
 }
 
-// bounce_walk_culled with the groups the keep test drops left out.
-RT_LIGHT_FN Bounce bounce_walk_grouped(const rt_scene& s, const rt_cube_bound* accel,
-                                       const rt_sphere_group* groups, int32_t num_groups,
-                                       int32_t obj, Vec3 p, Vec3 R) {
-    Bounce b{kFar, -1, -1};
-    const double pd[3] = {p.x, p.y, p.z};
-    const double Rd[3] = {R.x, R.y, R.z};
-    float sf;
-    for (int32_t j = 0; j < s.num_cubes; ++j) {
-        if (j == obj || !cube_kept(pd, Rd, accel[j], false)) continue;
-        const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
-        for (int k = 0; k < 12; ++k)
-            if (bounce_tri(pd, Rd, v + 12 * k, &sf) && sf < b.best) b = Bounce{sf, j, k};
+// CubeCull's cube phase, and the sphere phase of both walks with the groups the
+// keep test drops left out.
+struct GroupCull {
+    static constexpr bool kGroups = true;
+    const rt_cube_bound* accel;
+    const rt_sphere_group* groups;
+    int32_t num_groups;
+    RT_LIGHT_FN bool cube(const double* o, const double* d, int32_t j, bool segment) const {
+        return cube_kept(o, d, accel[j], segment);
     }
-    for (int32_t g = 0; g < num_groups; ++g) {
-        const rt_sphere_group& G = groups[g];
-        if (!group_kept(pd, Rd, G, false)) continue;
-        for (int k = 0; k < kGroupMax && k < G.count; ++k) {
-            const int32_t i = G.member[k];
-            // (a foreign record's index is no sphere)
-            if (static_cast<uint32_t>(i) >= static_cast<uint32_t>(s.num_spheres)) continue;
-            if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
-            if (bounce_sphere(p, R, s.sphere_origins + 4 * static_cast<int64_t>(i),
-                              s.sphere_radius[i], &sf) &&
-                sphere_takes(b, sf, s.num_cubes + i, s.num_cubes))
-                b = Bounce{sf, s.num_cubes + i, -1};
+    // bounce_walk's sphere phase: `b` is the best of the cubes.
+    RT_LIGHT_FN Bounce bounce_spheres(const rt_scene& s, const double* pd, const double* Rd,
+                                      int32_t obj, Vec3 p, Vec3 R, Bounce b) const {
+        float sf;
+        for (int32_t g = 0; g < num_groups; ++g) {
+            const rt_sphere_group& G = groups[g];
+            if (!group_kept(pd, Rd, G, false)) continue;
+            for (int k = 0; k < kGroupMax && k < G.count; ++k) {
+                const int32_t i = G.member[k];
+                // (a foreign record's index is no sphere)
+                if (static_cast<uint32_t>(i) >= static_cast<uint32_t>(s.num_spheres)) continue;
+                if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
+                if (bounce_sphere(p, R, s.sphere_origins + 4 * static_cast<int64_t>(i),
+                                  s.sphere_radius[i], &sf) &&
+                    sphere_takes(b, sf, s.num_cubes + i, s.num_cubes))
+                    b = Bounce{sf, s.num_cubes + i, -1};
+            }
         }
+        return b;
     }
-    return b;
-}
+    // light_occluded's sphere phase.
+    RT_LIGHT_FN bool occluded_by_spheres(const rt_scene& s, const double* pd, const double* Ld,
+                                         int32_t obj, Vec3 p, Vec3 L) const {
+        for (int32_t g = 0; g < num_groups; ++g) {
+            const rt_sphere_group& G = groups[g];
+            if (!group_kept(pd, Ld, G, true)) continue;
+            for (int k = 0; k < kGroupMax && k < G.count; ++k) {
+                const int32_t i = G.member[k];
+                if (static_cast<uint32_t>(i) >= static_cast<uint32_t>(s.num_spheres)) continue;
+                if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
+                if (occluded_by_sphere(p, L, s.sphere_origins + 4 * static_cast<int64_t>(i),
+                                       s.sphere_radius[i]))
+                    return true;
+            }
+        }
+        return false;
+    }
+};
 
-// light_occluded_culled with the groups the keep test drops left out.
-RT_LIGHT_FN bool light_occluded_grouped(const rt_scene& s, const rt_cube_bound* accel,
-                                        const rt_sphere_group* groups, int32_t num_groups,
-                                        int32_t obj, Vec3 p, Vec3 L) {
-    const double pd[3] = {p.x, p.y, p.z};
-    const double Ld[3] = {L.x, L.y, L.z};
-    for (int32_t j = 0; j < s.num_cubes; ++j) {
-        if (j == obj || !cube_kept(pd, Ld, accel[j], true)) continue;
-        const float* v = s.cube_vertices + 144 * static_cast<int64_t>(j);
-        for (int k = 0; k < 12; ++k)
-            if (occluded_by_tri(pd, Ld, v + 12 * k)) return true;
-    }
-    for (int32_t g = 0; g < num_groups; ++g) {
-        const rt_sphere_group& G = groups[g];
-        if (!group_kept(pd, Ld, G, true)) continue;
-        for (int k = 0; k < kGroupMax && k < G.count; ++k) {
-            const int32_t i = G.member[k];
-            if (static_cast<uint32_t>(i) >= static_cast<uint32_t>(s.num_spheres)) continue;
-            if (static_cast<int64_t>(s.num_cubes) + i == obj) continue;
-            if (occluded_by_sphere(p, L, s.sphere_origins + 4 * static_cast<int64_t>(i),
-                                   s.sphere_radius[i]))
-                return true;
-        }
-    }
-    return false;
-}
+// The pair of walks of the *_grouped calls.  GroupedWalks{accel, groups, num_groups}.
+using GroupedWalks = WalksOver<GroupCull>;
 
 }  // namespace rt_light
 

@@ -840,6 +840,33 @@ def _rays(rays: np.ndarray) -> np.ndarray:
     return rays
 
 
+def _per_ray(call: str, rays: np.ndarray, scene: Scene, cull: tuple, dtype, triangles=None):
+    """A host ray query with one `dtype` output per ray, in the rays' shape:
+    library().<call>(rays, n, scene, *cull, out[, triangles]).  `triangles`:
+    None where the call takes no triangle array, else whether to return one."""
+    out = np.empty(rays.shape, dtype)
+    tri = np.empty(rays.shape, np.int32) if triangles else None
+    sc = scene.as_c()
+    tail = () if triangles is None else (_ptr(tri),)
+    _check(getattr(library(), call)(_ptr(rays), rays.size, ctypes.byref(sc), *cull, _ptr(out),
+                                    *tail), call)
+    return (out, tri) if triangles else out
+
+
+def _per_pixel(call: str, camera: "Camera", scene: Scene, cull: tuple, width: int, height: int,
+               rows: Optional[Tuple[int, int]], triangles: bool):
+    """A host camera cast with a (rows x width) HIT_DTYPE frame:
+    library().<call>(camera, scene, *cull, width, row_begin, row_end, out, triangles)."""
+    rb, re = rows if rows is not None else (0, height)
+    shape = (max(re - rb, 0), max(width, 0))
+    out = np.empty(shape, HIT_DTYPE)
+    tri = np.empty(shape, np.int32) if triangles else None
+    c, sc = camera.as_c(), scene.as_c()
+    _check(getattr(library(), call)(ctypes.byref(c), ctypes.byref(sc), *cull, width, rb, re,
+                                    _ptr(out), _ptr(tri)), call)
+    return (out, tri) if triangles else out
+
+
 def cast_rays(rays: np.ndarray, scene: Scene, triangles: bool = False):
     """rt_cast_rays: per ray (RAY_DTYPE, any shape) the closest hit from its
     origin along its direction over every object of `scene` but its `skip`, as
@@ -847,25 +874,14 @@ def cast_rays(rays: np.ndarray, scene: Scene, triangles: bool = False):
     direction and the colour slot, (HIT_MISS_T, -1) for a miss.
     triangles=True: (hits, int32 array of the cube triangle met, -1 on a
     sphere or a miss).  On the host."""
-    rays = _rays(rays)
-    out = np.empty(rays.shape, HIT_DTYPE)
-    tri = np.empty(rays.shape, np.int32) if triangles else None
-    sc = scene.as_c()
-    _check(library().rt_cast_rays(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(out), _ptr(tri)),
-           "rt_cast_rays")
-    return (out, tri) if triangles else out
+    return _per_ray("rt_cast_rays", _rays(rays), scene, (), HIT_DTYPE, triangles)
 
 
 def occlude_rays(rays: np.ndarray, scene: Scene) -> np.ndarray:
     """rt_occlude_rays: per ray a uint8, 1 iff an object of `scene` other than
     its `skip` cuts the open segment from its origin to origin + direction.
     On the host."""
-    rays = _rays(rays)
-    out = np.empty(rays.shape, np.uint8)
-    sc = scene.as_c()
-    _check(library().rt_occlude_rays(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(out)),
-           "rt_occlude_rays")
-    return out
+    return _per_ray("rt_occlude_rays", _rays(rays), scene, (), np.uint8)
 
 
 def camera_rays(camera: Camera, width: int, height: int,
@@ -884,14 +900,7 @@ def cast_camera(camera: Camera, scene: Scene, width: int, height: int,
     """rt_cast_camera: cast_rays on camera_rays' rays, without the rays: a
     (rows x width) HIT_DTYPE frame (with triangles=True, and the int32
     triangles).  On the host."""
-    rb, re = rows if rows is not None else (0, height)
-    shape = (max(re - rb, 0), max(width, 0))
-    out = np.empty(shape, HIT_DTYPE)
-    tri = np.empty(shape, np.int32) if triangles else None
-    c, sc = camera.as_c(), scene.as_c()
-    _check(library().rt_cast_camera(ctypes.byref(c), ctypes.byref(sc), width, rb, re, _ptr(out),
-                                    _ptr(tri)), "rt_cast_camera")
-    return (out, tri) if triangles else out
+    return _per_pixel("rt_cast_camera", camera, scene, (), width, height, rows, triangles)
 
 
 def _accel(accel: np.ndarray, scene: Scene) -> np.ndarray:
@@ -918,34 +927,21 @@ def accel_kept(rays: np.ndarray, scene: Scene, accel: np.ndarray,
     that the keep test keeps (segment=False: cast_rays_accel's test, True:
     occlude_rays_accel's).  On the host."""
     rays, accel = _rays(rays), _accel(accel, scene)
-    out = np.empty(rays.shape, np.int32)
-    sc = scene.as_c()
-    _check(library().rt_accel_kept(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
-                                   int(bool(segment)), _ptr(out)), "rt_accel_kept")
-    return out
+    return _per_ray("rt_accel_kept", rays, scene, (_ptr(accel), int(bool(segment))), np.int32)
 
 
 def cast_rays_accel(rays: np.ndarray, scene: Scene, accel: np.ndarray, triangles: bool = False):
     """rt_cast_rays_accel: cast_rays' result word for word, with the cubes that
     `accel` (build_accel(scene)) proves missed left out per ray.  On the host."""
     rays, accel = _rays(rays), _accel(accel, scene)
-    out = np.empty(rays.shape, HIT_DTYPE)
-    tri = np.empty(rays.shape, np.int32) if triangles else None
-    sc = scene.as_c()
-    _check(library().rt_cast_rays_accel(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
-                                        _ptr(out), _ptr(tri)), "rt_cast_rays_accel")
-    return (out, tri) if triangles else out
+    return _per_ray("rt_cast_rays_accel", rays, scene, (_ptr(accel),), HIT_DTYPE, triangles)
 
 
 def occlude_rays_accel(rays: np.ndarray, scene: Scene, accel: np.ndarray) -> np.ndarray:
     """rt_occlude_rays_accel: occlude_rays' result word for word, culled by
     `accel`.  On the host."""
     rays, accel = _rays(rays), _accel(accel, scene)
-    out = np.empty(rays.shape, np.uint8)
-    sc = scene.as_c()
-    _check(library().rt_occlude_rays_accel(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
-                                           _ptr(out)), "rt_occlude_rays_accel")
-    return out
+    return _per_ray("rt_occlude_rays_accel", rays, scene, (_ptr(accel),), np.uint8)
 
 
 def cast_camera_accel(camera: Camera, scene: Scene, accel: np.ndarray, width: int, height: int,
@@ -953,14 +949,8 @@ def cast_camera_accel(camera: Camera, scene: Scene, accel: np.ndarray, width: in
     """rt_cast_camera_accel: cast_camera's frame word for word, culled by
     `accel`.  On the host."""
     accel = _accel(accel, scene)
-    rb, re = rows if rows is not None else (0, height)
-    shape = (max(re - rb, 0), max(width, 0))
-    out = np.empty(shape, HIT_DTYPE)
-    tri = np.empty(shape, np.int32) if triangles else None
-    c, sc = camera.as_c(), scene.as_c()
-    _check(library().rt_cast_camera_accel(ctypes.byref(c), ctypes.byref(sc), _ptr(accel), width,
-                                          rb, re, _ptr(out), _ptr(tri)), "rt_cast_camera_accel")
-    return (out, tri) if triangles else out
+    return _per_pixel("rt_cast_camera_accel", camera, scene, (_ptr(accel),), width, height, rows,
+                      triangles)
 
 
 def _groups(groups: np.ndarray) -> np.ndarray:
@@ -991,12 +981,8 @@ def sphere_groups_kept(rays: np.ndarray, scene: Scene, groups: np.ndarray,
     test keeps (segment=False: cast_rays_grouped's test, True:
     occlude_rays_grouped's).  On the host."""
     rays, groups = _rays(rays), _groups(groups)
-    out = np.empty(rays.shape, np.int32)
-    sc = scene.as_c()
-    _check(library().rt_sphere_groups_kept(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(groups),
-                                           groups.size, int(bool(segment)), _ptr(out)),
-           "rt_sphere_groups_kept")
-    return out
+    return _per_ray("rt_sphere_groups_kept", rays, scene,
+                    (_ptr(groups), groups.size, int(bool(segment))), np.int32)
 
 
 def cast_rays_grouped(rays: np.ndarray, scene: Scene, accel: np.ndarray, groups: np.ndarray,
@@ -1005,13 +991,8 @@ def cast_rays_grouped(rays: np.ndarray, scene: Scene, accel: np.ndarray, groups:
     (build_accel(scene)) and with the sphere groups that `groups`
     (build_sphere_groups(scene)) proves missed left out per ray.  On the host."""
     rays, accel, groups = _rays(rays), _accel(accel, scene), _groups(groups)
-    out = np.empty(rays.shape, HIT_DTYPE)
-    tri = np.empty(rays.shape, np.int32) if triangles else None
-    sc = scene.as_c()
-    _check(library().rt_cast_rays_grouped(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
-                                          _ptr(groups), groups.size, _ptr(out), _ptr(tri)),
-           "rt_cast_rays_grouped")
-    return (out, tri) if triangles else out
+    return _per_ray("rt_cast_rays_grouped", rays, scene, (_ptr(accel), _ptr(groups), groups.size),
+                    HIT_DTYPE, triangles)
 
 
 def occlude_rays_grouped(rays: np.ndarray, scene: Scene, accel: np.ndarray,
@@ -1019,12 +1000,8 @@ def occlude_rays_grouped(rays: np.ndarray, scene: Scene, accel: np.ndarray,
     """rt_occlude_rays_grouped: occlude_rays' result word for word, culled by
     `accel` and `groups`.  On the host."""
     rays, accel, groups = _rays(rays), _accel(accel, scene), _groups(groups)
-    out = np.empty(rays.shape, np.uint8)
-    sc = scene.as_c()
-    _check(library().rt_occlude_rays_grouped(_ptr(rays), rays.size, ctypes.byref(sc), _ptr(accel),
-                                             _ptr(groups), groups.size, _ptr(out)),
-           "rt_occlude_rays_grouped")
-    return out
+    return _per_ray("rt_occlude_rays_grouped", rays, scene,
+                    (_ptr(accel), _ptr(groups), groups.size), np.uint8)
 
 
 def cast_camera_grouped(camera: Camera, scene: Scene, accel: np.ndarray, groups: np.ndarray,
@@ -1033,15 +1010,8 @@ def cast_camera_grouped(camera: Camera, scene: Scene, accel: np.ndarray, groups:
     """rt_cast_camera_grouped: cast_camera's frame word for word, culled by
     `accel` and `groups`.  On the host."""
     accel, groups = _accel(accel, scene), _groups(groups)
-    rb, re = rows if rows is not None else (0, height)
-    shape = (max(re - rb, 0), max(width, 0))
-    out = np.empty(shape, HIT_DTYPE)
-    tri = np.empty(shape, np.int32) if triangles else None
-    c, sc = camera.as_c(), scene.as_c()
-    _check(library().rt_cast_camera_grouped(ctypes.byref(c), ctypes.byref(sc), _ptr(accel),
-                                            _ptr(groups), groups.size, width, rb, re, _ptr(out),
-                                            _ptr(tri)), "rt_cast_camera_grouped")
-    return (out, tri) if triangles else out
+    return _per_pixel("rt_cast_camera_grouped", camera, scene,
+                      (_ptr(accel), _ptr(groups), groups.size), width, height, rows, triangles)
 
 
 def shadow_hits_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray,

@@ -5,89 +5,20 @@
 // of include/rt_accel_impl.h on the cube's prebuilt record, the text the host
 // functions compile.
 //
-// The walks are rt_accel_walks.inc's, which the culled light pass shares: they
-// stay wave-uniform, so the scene and now the record (320 bytes per cube) come
-// through scalar loads, once per wave.  The ballot skips a cube where no lane
-// of the wave keeps it, so coherent rays profit most.
+// The walks are rt_light_device.inc's over CubeCull of rt_accel_impl.h,
+// which the culled light pass shares: they stay wave-uniform, so the scene and
+// now the record (320 bytes per cube) come through scalar loads, once per wave.
+// The ballot skips a cube where no lane of the wave keeps it, so coherent rays
+// profit most.
 //
-// The ray prologues and the launch are rt_rays.hip's, restated here so that
-// that file and its kernels stay as they are.
+// The ray prologues, cast_kernel, occlude_kernel, the launch and the build's
+// reduce are rt_rays_device.inc's; here the kernels take the records as their
+// one cull argument.
 #include "rt_light_device.inc"
 #include "rt_accel_impl.h"
-#include "rt_accel_walks.inc"
+#include "rt_rays_device.inc"
 
 namespace {
-
-enum { kFromRays = 0, kFromCamera = 1 };
-
-// Ray i of a ray array: two 16-byte loads.
-__device__ __forceinline__ rt_light::Ray load_ray(const rt_ray* __restrict__ rays, int64_t i,
-                                                  const rt_scene& s, int32_t& skip) {
-    const float4* r = reinterpret_cast<const float4*>(rays) + 2 * i;
-    const float4 a = r[0], b = r[1];
-    skip = rt_light::ray_skip(s, __float_as_int(a.w));
-    return rt_light::Ray{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
-}
-
-// Ray i of a camera's band of n = rows * width pixels.
-__device__ __forceinline__ rt_light::Ray camera_ray_at(const rt_camera& cam, int64_t i, int64_t n,
-                                                       int32_t width, int32_t row_begin) {
-    int32_t x, r;
-    if (n <= (int64_t)UINT32_MAX) {  // (uniform) the 32-bit division is several times cheaper
-        const uint32_t q = (uint32_t)i / (uint32_t)width;
-        r = (int32_t)q;
-        x = (int32_t)((uint32_t)i - q * (uint32_t)width);
-    } else {
-        const int64_t q = i / width;
-        r = (int32_t)q;
-        x = (int32_t)(i - q * width);
-    }
-    return rt_light::camera_ray(cam, (float)x, (float)(row_begin + r));  // exact: both <= 2^24
-}
-
-// cast_kernel of rt_rays.hip over the culled walk.
-template <int kSource>
-__global__ void __launch_bounds__(256)
-cast_accel_kernel(const rt_ray* __restrict__ rays, rt_hit* __restrict__ out_hits,
-                  int32_t* __restrict__ out_triangle, const rt_cube_bound* __restrict__ accel,
-                  int64_t n, int32_t width, int32_t row_begin, rt_camera cam, rt_scene s) {
-    const int64_t i = pixel_index();
-    const bool live = i < n;
-    rt_light::Ray r{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-    int32_t skip = -1;
-    if constexpr (kSource == kFromRays) {
-        if (live) r = load_ray(rays, i, s, skip);
-    } else {
-        r = camera_ray_at(cam, i, n, width, row_begin);
-        // the ray is six opaque registers from here on, as in rt_rays.hip
-        asm("" : "+v"(r.o.x), "+v"(r.o.y), "+v"(r.o.z), "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z));
-    }
-    const rt_light::Bounce b = wave_bounce_walk_culled(s, accel, r.o, r.d, skip, live);
-    if (live) {
-        reinterpret_cast<int2*>(out_hits)[i] = make_int2(__float_as_int(b.best), b.obj2);
-        if (out_triangle) out_triangle[i] = b.tri2;
-    }
-}
-
-// occlude_kernel of rt_rays.hip over the culled walk.
-__global__ void __launch_bounds__(256)
-occlude_accel_kernel(const rt_ray* __restrict__ rays, uint8_t* __restrict__ out,
-                     const rt_cube_bound* __restrict__ accel, int64_t n, rt_scene s) {
-    const int64_t i = pixel_index();
-    const bool live = i < n;
-    rt_light::Ray r{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-    int32_t skip = -1;
-    if (live) r = load_ray(rays, i, s, skip);
-    const double pd[3] = {r.o.x, r.o.y, r.o.z};
-    const bool clear = occluder_walk_culled(s, accel, pd, r.o, r.d, skip, live);
-    if (live) out[i] = clear ? 0 : 1;
-}
-
-template <typename T, typename F>
-__device__ __forceinline__ T wave_reduce(T v, F f) {
-    for (int m = 32; m >= 1; m >>= 1) v = f(v, __shfl_xor(v, m));
-    return v;
-}
 
 // rt_light::cube_bound for a wave: one wave per cube, four per workgroup.
 // Lanes 0..35 hold one vertex each (one coalesced 576-byte read; the lanes
@@ -117,17 +48,17 @@ accel_build_kernel(const float* __restrict__ cube_vertices, rt_cube_bound* __res
         emax = l1 > l2 ? l1 : l2;
         rt_light::tri_normal(tri, nrm);
     }
-    const auto fmin_ = [](float a, float b) { return b < a ? b : a; };
-    const auto fmax_ = [](float a, float b) { return b > a ? b : a; };
     const float inf = __builtin_huge_valf();
     float4 lo, hi;
     if (finite) {
         // (+ 0.0f: a zero bound is +0 whichever of -0 and +0 the order met first)
-        lo = make_float4(wave_reduce(v.x, fmin_) + 0.0f, wave_reduce(v.y, fmin_) + 0.0f,
-                         wave_reduce(v.z, fmin_) + 0.0f, 0.0f);
-        hi = make_float4(wave_reduce(v.x, fmax_) + 0.0f, wave_reduce(v.y, fmax_) + 0.0f,
-                         wave_reduce(v.z, fmax_) + 0.0f, 0.0f);
-        emax = wave_reduce(emax, [](double a, double b) { return b > a ? b : a; });
+        lo = make_float4(lanes_reduce(v.x, 32, MinOf{}) + 0.0f,
+                         lanes_reduce(v.y, 32, MinOf{}) + 0.0f,
+                         lanes_reduce(v.z, 32, MinOf{}) + 0.0f, 0.0f);
+        hi = make_float4(lanes_reduce(v.x, 32, MaxOf{}) + 0.0f,
+                         lanes_reduce(v.y, 32, MaxOf{}) + 0.0f,
+                         lanes_reduce(v.z, 32, MaxOf{}) + 0.0f, 0.0f);
+        emax = lanes_reduce(emax, 32, MaxOf{});
         lo.w = rt_light::float_up(emax);
     } else {
         lo = make_float4(-inf, -inf, -inf, inf);
@@ -144,18 +75,6 @@ accel_build_kernel(const float* __restrict__ cube_vertices, rt_cube_bound* __res
         nk[1] = nrm[1];
         nk[2] = nrm[2];
     }
-}
-
-// What every ray entry point does after its checks (launch_rays of rt_rays.hip).
-template <typename Enqueue>
-int launch_rays(rt_ctx* ctx, int64_t n, int64_t per_block, void* stream, Enqueue enqueue) {
-    if (n == 0) return RT_OK;
-    const int64_t blocks = (n + per_block - 1) / per_block;  // (<= INT32_MAX: the checks)
-    if (hipSetDevice(rt_internal::ctx_device(ctx)) != hipSuccess) return RT_ERR_HIP;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : rt_internal::ctx_stream(ctx);
-    if (!st) return RT_ERR_HIP;
-    enqueue(dim3((unsigned)blocks), st);
-    return hipGetLastError() == hipSuccess ? RT_OK : RT_ERR_HIP;
 }
 
 }  // namespace
@@ -183,7 +102,7 @@ int rt_cast_rays_accel_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t n,
     if (!rc) rc = rt_light::check_accel(device_scene, device_accel);
     if (rc) return rc;
     return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
-        cast_accel_kernel<kFromRays><<<grid, dim3(256), 0, st>>>(
+        cast_kernel<kFromRays, const rt_cube_bound*><<<grid, dim3(256), 0, st>>>(
             device_rays, device_out_hits, device_out_triangle, device_accel, n, 1, 0, rt_camera{},
             *device_scene);
     });
@@ -197,8 +116,8 @@ int rt_occlude_rays_accel_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t
     if (!rc) rc = rt_light::check_accel(device_scene, device_accel);
     if (rc) return rc;
     return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
-        occlude_accel_kernel<<<grid, dim3(256), 0, st>>>(device_rays, device_out_occluded,
-                                                         device_accel, n, *device_scene);
+        occlude_kernel<const rt_cube_bound*><<<grid, dim3(256), 0, st>>>(
+            device_rays, device_out_occluded, device_accel, n, *device_scene);
     });
 }
 
@@ -213,7 +132,7 @@ int rt_cast_camera_accel_device(rt_ctx* ctx, const rt_camera* camera, const rt_s
     if (rc) return rc;
     const int64_t n = (int64_t)(row_end - row_begin) * width;
     return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
-        cast_accel_kernel<kFromCamera><<<grid, dim3(256), 0, st>>>(
+        cast_kernel<kFromCamera, const rt_cube_bound*><<<grid, dim3(256), 0, st>>>(
             nullptr, device_out_hits, device_out_triangle, device_accel, n, width, row_begin,
             *camera, *device_scene);
     });

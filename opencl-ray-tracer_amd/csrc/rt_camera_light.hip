@@ -1,14 +1,14 @@
 // rt_camera_light.hip -- rt_light_camera_device / rt_bounce_camera_device: the
 // light pass of a camera view on the device.  The mirror
 // chain of rt_light_accel.hip / rt_mirror.hip with level 0 found by a cast of
-// the pixel's own ray (cast_kernel<kFromCamera> of rt_rays.hip) instead of
-// read from a hit frame: one launch, no hit frame, no workspace, and no fp64
-// re-identification of the level-0 triangle.
+// the pixel's own ray (cast_kernel<kFromCamera>'s, by camera_ray_at of
+// rt_rays_device.inc) instead of read from a hit frame: one launch, no hit
+// frame, no workspace, and no fp64 re-identification of the level-0 triangle.
 //
 // One kernel template over the output (int32x4, RGBA8, bounce frame) and over
-// the walks (unculled: rt_light_device.inc; culled: rt_accel_walks.inc on the
-// prebuilt records).  One pixel per lane in 256-thread workgroups.  The ballots,
-// the LDS blend stack (depth * 4 KiB of dynamic shared memory; none for the
+// the walks of rt_light_device.inc (unculled, or culled by CubeCull of
+// rt_accel_impl.h on the prebuilt records).  One pixel per lane in 256-thread
+// workgroups.  The ballots, the LDS blend stack (depth * 4 KiB of dynamic shared memory; none for the
 // bounce frame) and the unwind are rt_light_accel.hip's, restated so that that
 // file and its kernels stay as they are.
 //
@@ -32,28 +32,14 @@
 #define RT_ACCEL_NORMALS_LOOP _Pragma("clang loop unroll(disable)")
 #endif
 #include "rt_accel_impl.h"
-#include "rt_accel_walks.inc"
+#include "rt_rays_device.inc"  // camera_ray_at
 #include "rt_camera_light_impl.h"
 
 namespace {
 
-enum { kOutBounce = 2 };
+using rt_light::CubeCull;
 
-// Ray i of a camera's band of n = rows * width pixels (camera_ray_at of rt_rays.hip).
-__device__ __forceinline__ rt_light::Ray camera_ray_at(const rt_camera& cam, int64_t i, int64_t n,
-                                                       int32_t width, int32_t row_begin) {
-    int32_t x, r;
-    if (n <= (int64_t)UINT32_MAX) {  // (uniform) the 32-bit division is several times cheaper
-        const uint32_t q = (uint32_t)i / (uint32_t)width;
-        r = (int32_t)q;
-        x = (int32_t)((uint32_t)i - q * (uint32_t)width);
-    } else {
-        const int64_t q = i / width;
-        r = (int32_t)q;
-        x = (int32_t)(i - q * width);
-    }
-    return rt_light::camera_ray(cam, (float)x, (float)(row_begin + r));  // exact: both <= 2^24
-}
+enum { kOutBounce = 2 };
 
 // The closest-hit walk of the instance, for the lanes that cast.
 template <bool kCulled>
@@ -62,7 +48,7 @@ __device__ __forceinline__ rt_light::Bounce walk(const rt_scene& s,
                                                  rt_light::Vec3 p, rt_light::Vec3 R, int32_t own,
                                                  bool casts) {
     if constexpr (kCulled)
-        return wave_bounce_walk_culled(s, accel, p, R, own, casts);
+        return wave_bounce_walk(s, p, R, own, casts, CubeCull{accel});
     else
         return wave_bounce_walk(s, p, R, own, casts);
 }
@@ -138,7 +124,7 @@ camera_light_kernel(rt_camera cam, int64_t n, int32_t width, int32_t row_begin,
                 if (shadows) {  // (uniform)
                     uint32_t unused = 0;
                     if constexpr (kCulled)
-                        k = light_walk_culled<false>(s, accel, p, nrm, cur, live, unused);
+                        k = light_walk<false>(s, p, nrm, cur, live, unused, CubeCull{accel});
                     else
                         k = light_walk<false>(s, p, nrm, cur, live, unused);
                 } else if (live) {

@@ -9,9 +9,9 @@
 // include/rt_light_run.h; each function is its
 // argument checks and the per-pixel call it hands to the loop.  Behind them the
 // ray queries, rt_cast_rays / rt_occlude_rays /
-// rt_camera_rays / rt_cast_camera: plain loops over bounce_walk, light_occluded
-// and the camera text of include/rt_rays_impl.h, and the checks they share with
-// rt_rays.hip.
+// rt_camera_rays / rt_cast_camera: the loops of include/rt_rays_run.h over the
+// unculled walks and the camera text of include/rt_rays_impl.h, and the checks
+// they share with rt_rays.hip.
 // Plain C++, no HIP.  The arithmetic is include/rt_light_impl.h, the text the
 // kernel compiles too; built with -ffp-contract=off like rt_scene.cpp.
 #include "rt_args.h"
@@ -19,6 +19,7 @@
 #include "rt_light_impl.h"
 #include "rt_light_run.h"
 #include "rt_rays_impl.h"
+#include "rt_rays_run.h"
 
 namespace rt_light {
 
@@ -31,12 +32,6 @@ int check(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32
     if (scene->num_lights > 0 && !scene->lights) return RT_ERR_INVALID_ARG;
     return RT_OK;
 }
-
-namespace {
-bool misaligned(const void* p, uintptr_t align) {
-    return reinterpret_cast<uintptr_t>(p) % align != 0;
-}
-}  // namespace
 
 int check_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, const void* out,
                uintptr_t out_align, const int32_t* triangle) {
@@ -76,30 +71,13 @@ using namespace rt_light;
 int rt_cast_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, rt_hit* out_hits,
                  int32_t* out_triangle) {
     const int rc = check_rays(rays, n, scene, out_hits, sizeof(rt_hit), out_triangle);
-    if (rc) return rc;
-    const rt_scene& s = *scene;
-    for (int64_t i = 0; i < n; ++i) {
-        const rt_ray& r = rays[i];
-        if (ray_skip(s, r.skip) != r.skip) return RT_ERR_INVALID_ARG;
-        const Bounce b = bounce_walk(s, r.skip, Vec3{r.ox, r.oy, r.oz}, Vec3{r.dx, r.dy, r.dz});
-        out_hits[i] = rt_hit{b.best, b.obj2};
-        if (out_triangle) out_triangle[i] = b.tri2;
-    }
-    return RT_OK;
+    return rc ? rc : cast_rays(rays, n, *scene, out_hits, out_triangle, Walks{});
 }
 
 // Is the open segment (o, o + d) of every ray cut: light_occluded, `skip` left out.
 int rt_occlude_rays(const rt_ray* rays, int64_t n, const rt_scene* scene, uint8_t* out_occluded) {
     const int rc = check_rays(rays, n, scene, out_occluded, 1, nullptr);
-    if (rc) return rc;
-    const rt_scene& s = *scene;
-    for (int64_t i = 0; i < n; ++i) {
-        const rt_ray& r = rays[i];
-        if (ray_skip(s, r.skip) != r.skip) return RT_ERR_INVALID_ARG;
-        out_occluded[i] =
-            light_occluded(s, r.skip, Vec3{r.ox, r.oy, r.oz}, Vec3{r.dx, r.dy, r.dz}) ? 1 : 0;
-    }
-    return RT_OK;
+    return rc ? rc : occlude_rays(rays, n, *scene, out_occluded, Walks{});
 }
 
 // The rays of a band of a camera's frame, row-major.
@@ -122,16 +100,9 @@ int rt_cast_camera(const rt_camera* camera, const rt_scene* scene, int32_t width
                    int32_t row_begin, int32_t row_end, rt_hit* out_hits, int32_t* out_triangle) {
     const int rc = check_camera(camera, scene, true, width, row_begin, row_end, out_hits,
                                 sizeof(rt_hit), out_triangle);
-    if (rc) return rc;
-    int64_t i = 0;
-    for (int32_t y = row_begin; y < row_end; ++y)
-        for (int32_t x = 0; x < width; ++x, ++i) {
-            const Ray r = camera_ray(*camera, static_cast<float>(x), static_cast<float>(y));
-            const Bounce b = bounce_walk(*scene, -1, r.o, r.d);
-            out_hits[i] = rt_hit{b.best, b.obj2};
-            if (out_triangle) out_triangle[i] = b.tri2;
-        }
-    return RT_OK;
+    return rc ? rc
+              : cast_camera(*camera, *scene, width, row_begin, row_end, out_hits, out_triangle,
+                            Walks{});
 }
 
 // The geometry of one bounce of the mirror chain.

@@ -1,8 +1,8 @@
 // rt_light_accel.hip -- rt_bounce_hits_accel_device /
 // rt_light_hits_mirrored_accel_device: the mirror chain of the deferred light
 // pass over the prebuilt cube records, on the device.
-// mirror_kernel (rt_mirror.hip) with the culled walks of rt_accel_walks.inc in
-// place of the unculled ones: a lane tests a cube only where it is not its own
+// mirror_kernel (rt_mirror.hip) with the walks of rt_light_device.inc culled by
+// CubeCull of rt_accel_impl.h: a lane tests a cube only where it is not its own
 // and the keep test of include/rt_accel_impl.h keeps it for the lane's shadow
 // segment or bounce.  What each call stores is its unculled call's output word
 // for word.  The mask, rt_shadow_hits_accel_device, is
@@ -32,9 +32,10 @@
 #define RT_ACCEL_NORMALS_LOOP _Pragma("clang loop unroll(disable)")
 #endif
 #include "rt_accel_impl.h"
-#include "rt_accel_walks.inc"
 
 namespace {
+
+using rt_light::CubeCull;
 
 enum { kOutBounce = 2 };
 
@@ -82,8 +83,9 @@ light_accel_kernel(const rt_hit* __restrict__ hits, const rt_cube_bound* __restr
 #pragma clang loop unroll(disable)
         for (int32_t j = 1; __ballot(live) != 0; ++j) {  // (uniform)
             const Vec3 R = rt_light::mirror_dir(nrm, D);
-            b = wave_bounce_walk_culled(s, accel, p, R, cur, live);  // (kFar, -1) for the others
-            if (j >= depth) break;                                   // (uniform)
+            // (kFar, -1) for the others
+            b = wave_bounce_walk(s, p, R, cur, live, CubeCull{accel});
+            if (j >= depth) break;  // (uniform)
             live = b.obj2 >= 0;
             if (live) next_level(s, b, R, p, nrm, D, cur);
         }
@@ -115,7 +117,7 @@ light_accel_kernel(const rt_hit* __restrict__ hits, const rt_cube_bound* __restr
                 if (lights) {  // (uniform)
                     if (shadows) {  // (uniform)
                         uint32_t unused = 0;
-                        k = light_walk_culled<false>(s, accel, p, nrm, cur, live, unused);
+                        k = light_walk<false>(s, p, nrm, cur, live, unused, CubeCull{accel});
                     } else if (live) {
                         k = rt_light::light_factor(nrm, p, s.lights, s.num_lights);
                     }
@@ -137,7 +139,7 @@ light_accel_kernel(const rt_hit* __restrict__ hits, const rt_cube_bound* __restr
                 }
                 deepest = j + 1;
                 const Vec3 R = rt_light::mirror_dir(nrm, D);
-                const rt_light::Bounce b = wave_bounce_walk_culled(s, accel, p, R, cur, goes);
+                const rt_light::Bounce b = wave_bounce_walk(s, p, R, cur, goes, CubeCull{accel});
                 live = goes && b.obj2 >= 0;  // a miss leaves C = (0, 0, 0)
                 if (live) {
                     T = T + b.best;

@@ -1,9 +1,18 @@
 // rt_light_device.inc -- what the kernels of the deferred light pass share
 // (DESIGN.md §3.1a-d): the pixel prologue, the wave-uniform surface step, the
 // shadow walk, the bounce walk, the lit store, and on the host the one launch
-// function and the preload helper.  Included once by each of rt_light.hip,
-// rt_shadow.hip, rt_reflect.hip and rt_shadow_reflect.hip, in front of their
-// kernel; not a standalone translation unit.
+// function and the preload helper.  Included once by every translation unit of
+// the light pass and of the ray queries, in front of its kernels; not a
+// standalone translation unit.
+//
+// Each walk is written once, over a cull policy passed by value: whether a
+// lane has to test a cube.  The policies are the host walks': KeepAll of
+// rt_light_impl.h, the unculled one and the default, and CubeCull of
+// rt_accel_impl.h, which asks the prebuilt cube records (DESIGN.md §3.1g,
+// §3.1h); WaveGroupCull of rt_sphere_groups.hip adds the shadow walk's loop
+// over the sphere groups (§3.1j; a policy with kGroups walks the spheres
+// itself).  A translation unit that culls includes rt_accel_impl.h itself,
+// behind this file (some set RT_ACCEL_NORMALS_LOOP first).
 //
 // The per-pixel arithmetic is include/rt_light_impl.h, the text the host
 // functions of rt_light.cpp compile, so the two agree bit for bit.  What is
@@ -31,6 +40,8 @@
 #pragma clang fp contract(off)  // (file scope: holds for the including file too)
 
 namespace {
+
+using rt_light::KeepAll;
 
 // The two lit outputs of every kernel template; each file's third kind
 // (surface, mask, bounce, mask2) is 2 under its own name.
@@ -92,15 +103,16 @@ __device__ __forceinline__ rt_light::Vec3 surface_step(const rt_scene& s, int32_
 // that are `pending`.  Returns whether the lane is still pending: not
 // occluded.  "Any occluder" does not depend on the order of the tests
 // (§3.1b), so the walk ends as soon as no lane of the wave is pending.
+template <typename Cull = KeepAll>
 __device__ __forceinline__ bool occluder_walk(const rt_scene& s, const double* pd,
                                               rt_light::Vec3 p, rt_light::Vec3 L, int32_t own,
-                                              bool pending) {
+                                              bool pending, Cull cull = Cull{}) {
     if (__ballot(pending) == 0) return pending;  // (uniform) no walk for this light
     const double Ld[3] = {L.x, L.y, L.z};
     for (int32_t j = 0; j < s.num_cubes; ++j) {
-        // the lane's own cube is skipped whole; a cube no pending lane has to
-        // test is skipped by the wave
-        const bool mine = pending && own != j;
+        // the lane's own cube and a cube its policy drops are skipped whole; a
+        // cube no pending lane has to test is skipped by the wave
+        const bool mine = pending && own != j && cull.cube(pd, Ld, j, true);
         if (__ballot(mine) == 0) continue;
         const float* v = s.cube_vertices + 144 * (int64_t)j;
         for (int tri = 0; tri < 12; ++tri) {
@@ -111,13 +123,17 @@ __device__ __forceinline__ bool occluder_walk(const rt_scene& s, const double* p
         if (__ballot(pending) == 0) break;
     }
     if (__ballot(pending) != 0) {
-        // (sphere sp is object num_cubes + sp; own < 2^31 so the sum fits)
-        for (int32_t sp = 0; sp < s.num_spheres; ++sp) {
-            if (pending && own - s.num_cubes != sp &&
-                rt_light::occluded_by_sphere(p, L, s.sphere_origins + 4 * (int64_t)sp,
-                                             s.sphere_radius[sp]))
-                pending = false;
-            if (__ballot(pending) == 0) break;
+        if constexpr (Cull::kGroups) {
+            pending = cull.occluder_spheres(s, pd, Ld, p, L, own, pending);
+        } else {
+            // (sphere sp is object num_cubes + sp; own < 2^31 so the sum fits)
+            for (int32_t sp = 0; sp < s.num_spheres; ++sp) {
+                if (pending && own - s.num_cubes != sp &&
+                    rt_light::occluded_by_sphere(p, L, s.sphere_origins + 4 * (int64_t)sp,
+                                                 s.sphere_radius[sp]))
+                    pending = false;
+                if (__ballot(pending) == 0) break;
+            }
         }
     }
     return pending;
@@ -126,10 +142,10 @@ __device__ __forceinline__ bool occluder_walk(const rt_scene& s, const double* p
 // shadowed_factor (and, with kMask, shadow_mask into `mask`) at the point `p`
 // with the faced normal `nrm` and own object `own`, for the lanes that are
 // `active`; 1 for the others.  s.num_lights > 0.
-template <bool kMask>
+template <bool kMask, typename Cull = KeepAll>
 __device__ __forceinline__ float light_walk(const rt_scene& s, rt_light::Vec3 p,
                                             rt_light::Vec3 nrm, int32_t own, bool active,
-                                            uint32_t& mask) {
+                                            uint32_t& mask, Cull cull = Cull{}) {
     using rt_light::Vec3;
     float k = 0.0f;
     const double pd[3] = {p.x, p.y, p.z};
@@ -139,7 +155,7 @@ __device__ __forceinline__ float light_walk(const rt_scene& s, rt_light::Vec3 p,
         const float ll = sqrtf((L.x * L.x + L.y * L.y) + L.z * L.z);
         const float c = ((nrm.x * L.x + nrm.y * L.y) + nrm.z * L.z) / ll;
         const bool faces = active && c > 0.0f;
-        const bool pending = occluder_walk(s, pd, p, L, own, faces);
+        const bool pending = occluder_walk(s, pd, p, L, own, faces, cull);
         if (faces) {
             if (pending)
                 k = k + c;  // not occluded
@@ -158,17 +174,18 @@ __device__ __forceinline__ float light_walk(const rt_scene& s, rt_light::Vec3 p,
 // the loop counters held, so they index the scene in range by construction.
 // reflect_kernel's walk; phase 2 of shadow_reflect_kernel keeps the same text
 // inline (measured: profiles/light_shared/README.md).
+template <typename Cull = KeepAll>
 __device__ __forceinline__ rt_light::Bounce wave_bounce_walk(const rt_scene& s, rt_light::Vec3 p,
                                                              rt_light::Vec3 R, int32_t own,
-                                                             bool casts) {
+                                                             bool casts, Cull cull = Cull{}) {
     rt_light::Bounce b{rt_light::kFar, -1, -1};
     const double pd[3] = {p.x, p.y, p.z};
     const double Rd[3] = {R.x, R.y, R.z};
     float sf;
     for (int32_t j = 0; j < s.num_cubes; ++j) {
-        // the lane's own cube is skipped whole; a cube no lane has to test is
-        // skipped by the wave
-        const bool mine = casts && own != j;
+        // the lane's own cube and a cube its policy drops are skipped whole; a
+        // cube no lane has to test is skipped by the wave
+        const bool mine = casts && own != j && cull.cube(pd, Rd, j, false);
         if (__ballot(mine) == 0) continue;
         const float* v = s.cube_vertices + 144 * (int64_t)j;
         for (int tri = 0; tri < 12; ++tri)

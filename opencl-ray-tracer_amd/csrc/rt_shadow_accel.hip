@@ -1,7 +1,7 @@
 // rt_shadow_accel.hip -- rt_shadow_hits_accel_device: the shadow mask of the
 // deferred light pass over the prebuilt cube records, on the device
 // (DESIGN.md §3.1h).  shadow_kernel's mask form (rt_shadow.hip) with
-// light_walk_culled of rt_accel_walks.inc in place of light_walk: a lane tests
+// light_walk culled by CubeCull of rt_accel_impl.h: a lane tests
 // a cube for a light only where the cube is not its own and the keep test of
 // include/rt_accel_impl.h keeps it for the lane's segment to that light.  The
 // mask is rt_shadow_hits_device's word for word.
@@ -18,9 +18,10 @@
 // loads it at the first launch of its kernel.
 #include "rt_light_device.inc"
 #include "rt_accel_impl.h"
-#include "rt_accel_walks.inc"
 
 namespace {
+
+using rt_light::CubeCull;
 
 // `s` holds device pointers, `accel` its s.num_cubes records.
 __global__ void __launch_bounds__(256)
@@ -43,7 +44,7 @@ shadow_accel_kernel(const rt_hit* __restrict__ hits, const rt_cube_bound* __rest
             p = rt_light::hit_point(ox, oy, d, t);
             nrm = surface_step(s, obj, ox, oy, d, t, p);
         }
-        light_walk_culled<true>(s, accel, p, nrm, obj, hit, mask);
+        light_walk<true>(s, p, nrm, obj, hit, mask, CubeCull{accel});
     }
     out[i] = mask;
 }

@@ -2,23 +2,18 @@
 // the host: rt_sphere_groups_count, rt_sphere_groups_build,
 // rt_sphere_groups_kept, rt_cast_rays_grouped, rt_occlude_rays_grouped and
 // rt_cast_camera_grouped, and the argument checks they share with
-// rt_sphere_groups.hip.  Plain loops over include/rt_sphere_groups_impl.h, the
-// text the kernels compile too.  Plain C++, no HIP; built with
+// rt_sphere_groups.hip.  The loops of include/rt_rays_run.h over GroupedWalks of
+// include/rt_sphere_groups_impl.h, the text the kernels compile too.  Plain C++, no HIP; built with
 // -ffp-contract=off like rt_accel.cpp.
 #include <algorithm>
 #include <vector>
 
 #include "rt_args.h"
 #include "rt_hip.h"
+#include "rt_rays_run.h"
 #include "rt_sphere_groups_impl.h"
 
 namespace rt_light {
-
-namespace {
-bool misaligned(const void* p, uintptr_t align) {
-    return reinterpret_cast<uintptr_t>(p) % align != 0;
-}
-}  // namespace
 
 int check_sphere_groups_build(const rt_scene* scene, int32_t group_size,
                               const rt_sphere_group* out) {
@@ -98,17 +93,10 @@ int rt_sphere_groups_kept(const rt_ray* rays, int64_t n, const rt_scene* scene,
     int rc = check_rays(rays, n, scene, out_count, 4, nullptr);
     if (!rc) rc = check_sphere_groups(scene, groups, num_groups);
     if (rc) return rc;
-    const rt_scene& s = *scene;
-    for (int64_t i = 0; i < n; ++i) {
-        const rt_ray& r = rays[i];
-        if (ray_skip(s, r.skip) != r.skip) return RT_ERR_INVALID_ARG;
-        const double o[3] = {r.ox, r.oy, r.oz}, d[3] = {r.dx, r.dy, r.dz};
-        int32_t kept = 0;
-        for (int32_t g = 0; g < num_groups; ++g)
-            if (group_kept(o, d, groups[g], segment != 0)) ++kept;
-        out_count[i] = kept;
-    }
-    return RT_OK;
+    return count_kept(rays, n, *scene, num_groups, out_count,
+                      [=](const double* o, const double* d, int32_t g, int32_t) {
+                          return group_kept(o, d, groups[g], segment != 0);
+                      });
 }
 
 int rt_cast_rays_grouped(const rt_ray* rays, int64_t n, const rt_scene* scene,
@@ -117,17 +105,9 @@ int rt_cast_rays_grouped(const rt_ray* rays, int64_t n, const rt_scene* scene,
     int rc = check_rays(rays, n, scene, out_hits, sizeof(rt_hit), out_triangle);
     if (!rc) rc = check_accel(scene, accel);
     if (!rc) rc = check_sphere_groups(scene, groups, num_groups);
-    if (rc) return rc;
-    const rt_scene& s = *scene;
-    for (int64_t i = 0; i < n; ++i) {
-        const rt_ray& r = rays[i];
-        if (ray_skip(s, r.skip) != r.skip) return RT_ERR_INVALID_ARG;
-        const Bounce b = bounce_walk_grouped(s, accel, groups, num_groups, r.skip,
-                                             Vec3{r.ox, r.oy, r.oz}, Vec3{r.dx, r.dy, r.dz});
-        out_hits[i] = rt_hit{b.best, b.obj2};
-        if (out_triangle) out_triangle[i] = b.tri2;
-    }
-    return RT_OK;
+    return rc ? rc
+              : cast_rays(rays, n, *scene, out_hits, out_triangle,
+                          GroupedWalks{accel, groups, num_groups});
 }
 
 int rt_occlude_rays_grouped(const rt_ray* rays, int64_t n, const rt_scene* scene,
@@ -136,17 +116,9 @@ int rt_occlude_rays_grouped(const rt_ray* rays, int64_t n, const rt_scene* scene
     int rc = check_rays(rays, n, scene, out_occluded, 1, nullptr);
     if (!rc) rc = check_accel(scene, accel);
     if (!rc) rc = check_sphere_groups(scene, groups, num_groups);
-    if (rc) return rc;
-    const rt_scene& s = *scene;
-    for (int64_t i = 0; i < n; ++i) {
-        const rt_ray& r = rays[i];
-        if (ray_skip(s, r.skip) != r.skip) return RT_ERR_INVALID_ARG;
-        out_occluded[i] = light_occluded_grouped(s, accel, groups, num_groups, r.skip,
-                                                 Vec3{r.ox, r.oy, r.oz}, Vec3{r.dx, r.dy, r.dz})
-                              ? 1
-                              : 0;
-    }
-    return RT_OK;
+    return rc ? rc
+              : occlude_rays(rays, n, *scene, out_occluded,
+                             GroupedWalks{accel, groups, num_groups});
 }
 
 int rt_cast_camera_grouped(const rt_camera* camera, const rt_scene* scene,
@@ -157,16 +129,9 @@ int rt_cast_camera_grouped(const rt_camera* camera, const rt_scene* scene,
                           out_triangle);
     if (!rc) rc = check_accel(scene, accel);
     if (!rc) rc = check_sphere_groups(scene, groups, num_groups);
-    if (rc) return rc;
-    int64_t i = 0;
-    for (int32_t y = row_begin; y < row_end; ++y)
-        for (int32_t x = 0; x < width; ++x, ++i) {
-            const Ray r = camera_ray(*camera, static_cast<float>(x), static_cast<float>(y));
-            const Bounce b = bounce_walk_grouped(*scene, accel, groups, num_groups, -1, r.o, r.d);
-            out_hits[i] = rt_hit{b.best, b.obj2};
-            if (out_triangle) out_triangle[i] = b.tri2;
-        }
-    return RT_OK;
+    return rc ? rc
+              : cast_camera(*camera, *scene, width, row_begin, row_end, out_hits, out_triangle,
+                            GroupedWalks{accel, groups, num_groups});
 }
 
 }  // extern "C"

@@ -11,48 +11,64 @@
 // scalar loads, once per wave.  A lane that does not keep a group does not
 // test it; the ballot skips a group where no lane of the wave keeps it.
 //
-// The cube phase is rt_accel_walks.inc's text, the ray prologues and the launch
-// are rt_accel.hip's, restated here so that those files and their kernels stay
-// as they are.  Not preloaded by rt_init (§3.1g Device).
+// The walks are rt_light_device.inc's over WaveGroupCull below: CubeCull of
+// rt_accel_impl.h in the cube phase, and the loop over the groups in place
+// of the walks' own sphere loop.  The ray prologues, cast_kernel,
+// occlude_kernel, the launch and the builds' reduce are rt_rays_device.inc's;
+// here the kernels take the cube records, the group records and their count as
+// cull arguments.  Not preloaded by rt_init (§3.1g Device).
 #include "rt_light_device.inc"
 #include "rt_accel_impl.h"
 #include "rt_sphere_groups_impl.h"
 
 namespace {
 
-enum { kFromRays = 0, kFromCamera = 1 };
-
-// Ray i of a ray array: two 16-byte loads.
-__device__ __forceinline__ rt_light::Ray load_ray(const rt_ray* __restrict__ rays, int64_t i,
-                                                  const rt_scene& s, int32_t& skip) {
-    const float4* r = reinterpret_cast<const float4*>(rays) + 2 * i;
-    const float4 a = r[0], b = r[1];
-    skip = rt_light::ray_skip(s, __float_as_int(a.w));
-    return rt_light::Ray{{a.x, a.y, a.z}, {b.x, b.y, b.z}};
-}
-
-// Ray i of a camera's band of n = rows * width pixels.
-__device__ __forceinline__ rt_light::Ray camera_ray_at(const rt_camera& cam, int64_t i, int64_t n,
-                                                       int32_t width, int32_t row_begin) {
-    int32_t x, r;
-    if (n <= (int64_t)UINT32_MAX) {  // (uniform) the 32-bit division is several times cheaper
-        const uint32_t q = (uint32_t)i / (uint32_t)width;
-        r = (int32_t)q;
-        x = (int32_t)((uint32_t)i - q * (uint32_t)width);
-    } else {
-        const int64_t q = i / width;
-        r = (int32_t)q;
-        x = (int32_t)(i - q * width);
+// CubeCull's cube phase, and the sphere phase over the groups: a lane tests the
+// members of group g iff it takes part and its ray keeps the group.
+struct WaveGroupCull : rt_light::CubeCull {
+    static constexpr bool kGroups = true;
+    const rt_sphere_group* __restrict__ groups;
+    int32_t num_groups;
+    // occluder_walk's sphere phase, entered with a pending lane in the wave;
+    // its early-outs stay.
+    __device__ __forceinline__ bool occluder_spheres(const rt_scene& s, const double* pd,
+                                                     const double* Ld, rt_light::Vec3 p,
+                                                     rt_light::Vec3 L, int32_t own,
+                                                     bool pending) const {
+        const int32_t own_sp = own - s.num_cubes;
+        for (int32_t g = 0; g < num_groups; ++g) {
+            const rt_sphere_group& G = groups[g];
+            const bool mine = pending && rt_light::group_kept(pd, Ld, G, true);
+            if (__ballot(mine) == 0) continue;
+            const int32_t count = G.count;
+            for (int k = 0; k < rt_light::kGroupMax && k < count; ++k) {
+                const int32_t sp = G.member[k];
+                if ((uint32_t)sp >= (uint32_t)s.num_spheres) continue;  // (uniform)
+                if (mine && pending && own_sp != sp &&
+                    rt_light::occluded_by_sphere(p, L, s.sphere_origins + 4 * (int64_t)sp,
+                                                 s.sphere_radius[sp]))
+                    pending = false;
+                if (__ballot(mine && pending) == 0) break;
+            }
+            if (__ballot(pending) == 0) break;
+        }
+        return pending;
     }
-    return rt_light::camera_ray(cam, (float)x, (float)(row_begin + r));  // exact: both <= 2^24
+};
+__device__ __forceinline__ WaveGroupCull cull_of(const rt_cube_bound* accel,
+                                             const rt_sphere_group* groups, int32_t num_groups) {
+    return WaveGroupCull{{accel}, groups, num_groups};
 }
 
-// wave_bounce_walk_culled of rt_accel_walks.inc, then the groups: a lane tests
-// the members of group g iff it casts and its ray keeps the group.
-__device__ __forceinline__ rt_light::Bounce wave_bounce_walk_grouped(
-    const rt_scene& s, const rt_cube_bound* __restrict__ accel,
-    const rt_sphere_group* __restrict__ groups, int32_t num_groups, rt_light::Vec3 p,
-    rt_light::Vec3 R, int32_t own, bool casts) {
+// wave_bounce_walk for WaveGroupCull: the shared walk's cube phase, then the groups.
+// Its own text, not a sphere phase of the policy as occluder_spheres is: that
+// wording missed the timing rule in cast_kernel (profiles/rays_shared/README.md).
+__device__ __forceinline__ rt_light::Bounce wave_bounce_walk(const rt_scene& s, rt_light::Vec3 p,
+                                                             rt_light::Vec3 R, int32_t own,
+                                                             bool casts, WaveGroupCull cull) {
+    const rt_cube_bound* __restrict__ accel = cull.accel;
+    const rt_sphere_group* __restrict__ groups = cull.groups;
+    const int32_t num_groups = cull.num_groups;
     rt_light::Bounce b{rt_light::kFar, -1, -1};
     const double pd[3] = {p.x, p.y, p.z};
     const double Rd[3] = {R.x, R.y, R.z};
@@ -86,89 +102,11 @@ __device__ __forceinline__ rt_light::Bounce wave_bounce_walk_grouped(
     return b;
 }
 
-// occluder_walk_culled of rt_accel_walks.inc, then the groups; its early-outs stay.
-__device__ __forceinline__ bool occluder_walk_grouped(const rt_scene& s,
-                                                      const rt_cube_bound* __restrict__ accel,
-                                                      const rt_sphere_group* __restrict__ groups,
-                                                      int32_t num_groups, const double* pd,
-                                                      rt_light::Vec3 p, rt_light::Vec3 L,
-                                                      int32_t own, bool pending) {
-    if (__ballot(pending) == 0) return pending;
-    const double Ld[3] = {L.x, L.y, L.z};
-    for (int32_t j = 0; j < s.num_cubes; ++j) {
-        const bool mine = pending && own != j && rt_light::cube_kept(pd, Ld, accel[j], true);
-        if (__ballot(mine) == 0) continue;
-        const float* v = s.cube_vertices + 144 * (int64_t)j;
-        for (int tri = 0; tri < 12; ++tri) {
-            if (mine && pending && rt_light::occluded_by_tri(pd, Ld, v + 12 * tri))
-                pending = false;
-            if (__ballot(mine && pending) == 0) break;
-        }
-        if (__ballot(pending) == 0) break;
-    }
-    if (__ballot(pending) != 0) {
-        const int32_t own_sp = own - s.num_cubes;
-        for (int32_t g = 0; g < num_groups; ++g) {
-            const rt_sphere_group& G = groups[g];
-            const bool mine = pending && rt_light::group_kept(pd, Ld, G, true);
-            if (__ballot(mine) == 0) continue;
-            const int32_t count = G.count;
-            for (int k = 0; k < rt_light::kGroupMax && k < count; ++k) {
-                const int32_t sp = G.member[k];
-                if ((uint32_t)sp >= (uint32_t)s.num_spheres) continue;  // (uniform)
-                if (mine && pending && own_sp != sp &&
-                    rt_light::occluded_by_sphere(p, L, s.sphere_origins + 4 * (int64_t)sp,
-                                                 s.sphere_radius[sp]))
-                    pending = false;
-                if (__ballot(mine && pending) == 0) break;
-            }
-            if (__ballot(pending) == 0) break;
-        }
-    }
-    return pending;
-}
+}  // namespace
 
-// cast_accel_kernel of rt_accel.hip over the grouped walk.
-template <int kSource>
-__global__ void __launch_bounds__(256)
-cast_grouped_kernel(const rt_ray* __restrict__ rays, rt_hit* __restrict__ out_hits,
-                    int32_t* __restrict__ out_triangle, const rt_cube_bound* __restrict__ accel,
-                    const rt_sphere_group* __restrict__ groups, int32_t num_groups, int64_t n,
-                    int32_t width, int32_t row_begin, rt_camera cam, rt_scene s) {
-    const int64_t i = pixel_index();
-    const bool live = i < n;
-    rt_light::Ray r{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-    int32_t skip = -1;
-    if constexpr (kSource == kFromRays) {
-        if (live) r = load_ray(rays, i, s, skip);
-    } else {
-        r = camera_ray_at(cam, i, n, width, row_begin);
-        // the ray is six opaque registers from here on, as in rt_rays.hip
-        asm("" : "+v"(r.o.x), "+v"(r.o.y), "+v"(r.o.z), "+v"(r.d.x), "+v"(r.d.y), "+v"(r.d.z));
-    }
-    const rt_light::Bounce b =
-        wave_bounce_walk_grouped(s, accel, groups, num_groups, r.o, r.d, skip, live);
-    if (live) {
-        reinterpret_cast<int2*>(out_hits)[i] = make_int2(__float_as_int(b.best), b.obj2);
-        if (out_triangle) out_triangle[i] = b.tri2;
-    }
-}
+#include "rt_rays_device.inc"
 
-// occlude_accel_kernel of rt_accel.hip over the grouped walk.
-__global__ void __launch_bounds__(256)
-occlude_grouped_kernel(const rt_ray* __restrict__ rays, uint8_t* __restrict__ out,
-                       const rt_cube_bound* __restrict__ accel,
-                       const rt_sphere_group* __restrict__ groups, int32_t num_groups, int64_t n,
-                       rt_scene s) {
-    const int64_t i = pixel_index();
-    const bool live = i < n;
-    rt_light::Ray r{{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
-    int32_t skip = -1;
-    if (live) r = load_ray(rays, i, s, skip);
-    const double pd[3] = {r.o.x, r.o.y, r.o.z};
-    const bool clear = occluder_walk_grouped(s, accel, groups, num_groups, pd, r.o, r.d, skip, live);
-    if (live) out[i] = clear ? 0 : 1;
-}
+namespace {
 
 // ---- the build: the workspace is a GroupFrame (16 bytes), then num_spheres
 // keys, then num_spheres sphere indices in sorted order ------------------------
@@ -178,12 +116,6 @@ __device__ __forceinline__ uint32_t* ws_keys(void* ws) {
 }
 __device__ __forceinline__ int32_t* ws_order(void* ws, int32_t n) {
     return reinterpret_cast<int32_t*>(ws_keys(ws) + n);
-}
-
-template <typename T, typename F>
-__device__ __forceinline__ T lanes_reduce(T v, int first, F f) {
-    for (int m = first; m >= 1; m >>= 1) v = f(v, __shfl_xor(v, m));
-    return v;
 }
 
 // Part 1, one workgroup: the minima and maxima of the finite spheres' centres
@@ -204,8 +136,8 @@ groups_frame_kernel(const float* __restrict__ sphere_origins,
             if (ctr[a] > mx[a]) mx[a] = ctr[a];
         }
     }
-    const auto fmin_ = [](float a, float b) { return b < a ? b : a; };
-    const auto fmax_ = [](float a, float b) { return b > a ? b : a; };
+    const MinOf fmin_{};
+    const MaxOf fmax_{};
     for (int a = 0; a < 3; ++a) {
         mn[a] = lanes_reduce(mn[a], 32, fmin_);
         mx[a] = lanes_reduce(mx[a], 32, fmax_);
@@ -294,8 +226,8 @@ groups_record_kernel(const float* __restrict__ sphere_origins,
             bad = 1.0f;
         }
     }
-    const auto fmin_ = [](float a, float b) { return b < a ? b : a; };
-    const auto fmax_ = [](float a, float b) { return b > a ? b : a; };
+    const MinOf fmin_{};
+    const MaxOf fmax_{};
     for (int a = 0; a < 3; ++a) {
         lo[a] = lanes_reduce(lo[a], 4, fmin_);
         hi[a] = lanes_reduce(hi[a], 4, fmax_);
@@ -326,18 +258,6 @@ groups_record_kernel(const float* __restrict__ sphere_origins,
         reinterpret_cast<float4*>(o)[1] = b;
     }
     o->member[slot] = holds ? idx : -1;  // (slot < 8: eight distinct (index, lane) pairs)
-}
-
-// What every ray entry point does after its checks (launch_rays of rt_rays.hip).
-template <typename Enqueue>
-int launch_rays(rt_ctx* ctx, int64_t n, int64_t per_block, void* stream, Enqueue enqueue) {
-    if (n == 0) return RT_OK;
-    const int64_t blocks = (n + per_block - 1) / per_block;  // (<= INT32_MAX: the checks)
-    if (hipSetDevice(rt_internal::ctx_device(ctx)) != hipSuccess) return RT_ERR_HIP;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : rt_internal::ctx_stream(ctx);
-    if (!st) return RT_ERR_HIP;
-    enqueue(dim3((unsigned)blocks), st);
-    return hipGetLastError() == hipSuccess ? RT_OK : RT_ERR_HIP;
 }
 
 }  // namespace
@@ -381,7 +301,8 @@ int rt_cast_rays_grouped_device(rt_ctx* ctx, const rt_ray* device_rays, int64_t 
     if (!rc) rc = rt_light::check_sphere_groups(device_scene, device_groups, num_groups);
     if (rc) return rc;
     return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
-        cast_grouped_kernel<kFromRays><<<grid, dim3(256), 0, st>>>(
+        cast_kernel<kFromRays, const rt_cube_bound*, const rt_sphere_group*, int32_t>
+            <<<grid, dim3(256), 0, st>>>(
             device_rays, device_out_hits, device_out_triangle, device_accel, device_groups,
             num_groups, n, 1, 0, rt_camera{}, *device_scene);
     });
@@ -397,9 +318,9 @@ int rt_occlude_rays_grouped_device(rt_ctx* ctx, const rt_ray* device_rays, int64
     if (!rc) rc = rt_light::check_sphere_groups(device_scene, device_groups, num_groups);
     if (rc) return rc;
     return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
-        occlude_grouped_kernel<<<grid, dim3(256), 0, st>>>(device_rays, device_out_occluded,
-                                                           device_accel, device_groups,
-                                                           num_groups, n, *device_scene);
+        occlude_kernel<const rt_cube_bound*, const rt_sphere_group*, int32_t>
+            <<<grid, dim3(256), 0, st>>>(device_rays, device_out_occluded, device_accel,
+                                         device_groups, num_groups, n, *device_scene);
     });
 }
 
@@ -417,7 +338,8 @@ int rt_cast_camera_grouped_device(rt_ctx* ctx, const rt_camera* camera,
     if (rc) return rc;
     const int64_t n = (int64_t)(row_end - row_begin) * width;
     return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
-        cast_grouped_kernel<kFromCamera><<<grid, dim3(256), 0, st>>>(
+        cast_kernel<kFromCamera, const rt_cube_bound*, const rt_sphere_group*, int32_t>
+            <<<grid, dim3(256), 0, st>>>(
             nullptr, device_out_hits, device_out_triangle, device_accel, device_groups,
             num_groups, n, width, row_begin, *camera, *device_scene);
     });
