@@ -213,6 +213,9 @@ struct CubeCull {
     }
 };
 RT_LIGHT_FN CubeCull cull_of(const rt_cube_bound* accel) { return CubeCull{accel}; }
+inline int check_cull(const rt_scene* scene, CubeCull cull) {
+    return check_accel(scene, cull.accel);
+}
 
 // rt_light_impl.h's Walks over the two culled walks: what the pixel functions
 // of the *_accel light pass take.  CulledWalks{accel}.

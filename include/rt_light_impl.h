@@ -37,6 +37,14 @@ namespace rt_light {
  * lights included.  csrc/rt_light.cpp. */
 int check(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32_t width,
           int32_t row_begin, int32_t row_end, const void* out);
+/* The settings of the lit chain entry points, host and device: the format,
+ * max_bounces, shadows, and a NULL reflectivity where a chain could read it.
+ * `scene` may be NULL (refused by the checks behind). */
+int check_chain_settings(const rt_scene* scene, const float* reflectivity, int32_t max_bounces,
+                         int32_t shadows, int32_t out_format);
+/* The host's scan of a reflectivity array (NULL: none): every value in [0, 1]
+ * (NaN is refused too); `mirrors`: one of them is not 0. */
+int check_reflectivity(const rt_scene& scene, const float* reflectivity, bool& mirrors);
 
 constexpr double kEpsilon = 0.000001;  // MainState.cpp:15
 constexpr float kFar = 300000.0f;      // MainState.cpp:345
@@ -255,6 +263,8 @@ struct KeepAll {
 };
 // The policy of a ray-query kernel's cull arguments (csrc/rt_rays_device.inc): none.
 RT_LIGHT_FN KeepAll cull_of() { return KeepAll{}; }
+// What a launch checks of its policy's arguments (the host, after the unculled checks).
+inline int check_cull(const rt_scene*, KeepAll) { return RT_OK; }
 
 // Does any object but `obj` (range-checked: a colour slot of `s`) occlude
 // the light at p + L?  The loops index 0 .. count-1 only; `obj` is compared.
@@ -653,51 +663,56 @@ RT_LIGHT_FN Vec3 chain_blend(Vec3 a, float r, Vec3 C) {
     return Vec3{a.x + r * (C.x - a.x), a.y + r * (C.y - a.y), a.z + r * (C.z - a.z)};
 }
 
+// The level the bounce `b` from p along R met, in place: its point, faced
+// normal and object.  R is the direction the level was reached along, which
+// the next bounce mirrors at the new normal: the second form keeps it as D.
+RT_LIGHT_FN void next_level(const rt_scene& s, Bounce b, Vec3 R, Vec3& p, Vec3& n, int32_t& obj) {
+    const Vec3 p2 = bounce_point(p, R, b.best);
+    n = bounce_normal(s, b.obj2, b.tri2, p2, R);
+    p = p2;
+    obj = b.obj2;
+}
+RT_LIGHT_FN void next_level(const rt_scene& s, Bounce b, Vec3 R, Vec3& p, Vec3& n, Vec3& D,
+                            int32_t& obj) {
+    next_level(s, b, R, p, n, obj);
+    D = R;
+}
+
+// The geometry of bounce number `bounce` (j .. RT_MAX_BOUNCES) of a chain whose
+// bounce number j leaves the reached level (p, n, D, obj), followed without
+// regard to reflectivity, lights or t.  (kFar, -1) where this bounce or an
+// earlier one met nothing.
+template <typename W>
+RT_LIGHT_FN Bounce bounce_chain_from(const rt_scene& s, Vec3 p, Vec3 n, Vec3 D, int32_t obj,
+                                     int32_t j, int32_t bounce, const W& w) {
+    for (;; ++j) {
+        const Vec3 R = mirror_dir(n, D);
+        const Bounce b = w.bounce(s, obj, p, R);
+        if (b.obj2 < 0 || j >= bounce) return b;
+        next_level(s, b, R, p, n, D, obj);
+    }
+}
+
 // The geometry of bounce number `bounce` (1 .. RT_MAX_BOUNCES) of one pixel's
-// chain, followed without regard to reflectivity, lights or t.  (kFar, -1) for
-// a miss and where this bounce or an earlier one met nothing.
+// chain; (kFar, -1) for a miss too.
 template <typename W = Walks>
 RT_LIGHT_FN Bounce bounce_chain_pixel(const rt_scene& s, int32_t obj, const float* verts, float ox,
                                       float oy, Vec3 d, float t, int32_t bounce,
                                       const W& w = W()) {
     if (obj < 0) return Bounce{kFar, -1, -1};
-    Vec3 p = hit_point(ox, oy, d, t);
+    const Vec3 p = hit_point(ox, oy, d, t);
     const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
-    Vec3 n{sf.nx, sf.ny, sf.nz};
-    Vec3 D = d;
-    for (int32_t j = 1;; ++j) {
-        const Vec3 R = mirror_dir(n, D);
-        const Bounce b = w.bounce(s, obj, p, R);
-        if (b.obj2 < 0 || j >= bounce) return b;
-        const Vec3 p2 = bounce_point(p, R, b.best);
-        n = bounce_normal(s, b.obj2, b.tri2, p2, R);
-        p = p2;
-        obj = b.obj2;
-        D = R;
-    }
+    return bounce_chain_from(s, p, Vec3{sf.nx, sf.ny, sf.nz}, d, obj, 1, bounce, w);
 }
 
-// One pixel of the mirrored frame (int32x4): a chain of at most `max_bounces`
-// (0 .. RT_MAX_BOUNCES) bounces, blended backwards.  `reflectivity` is read at
-// the slots of levels below max_bounces only.  A miss, and t == kFar, are
-// lit_pixel's (with `shadows`, lit_pixel_shadowed's).
-template <typename W = Walks>
-RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float* verts, float ox,
-                                    float oy, Vec3 d, float t, const float* reflectivity,
-                                    int32_t max_bounces, bool shadows, int32_t out[4],
-                                    const W& w = W()) {
-    if (obj < 0 || t == kFar) {
-        if (shadows)
-            lit_pixel_shadowed(s, obj, verts, ox, oy, d, t, out, w);
-        else
-            lit_pixel(s, obj, verts, ox, oy, d, t, out);
-        return;
-    }
-    Vec3 p = hit_point(ox, oy, d, t);
-    const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
-    Vec3 n{sf.nx, sf.ny, sf.nz};
-    Vec3 D = d;
-    float T = t;
+// The level loop and the backward blend of a chain of at most `max_bounces`
+// (0 .. RT_MAX_BOUNCES) bounces from the reached level 0 (p, n, D, obj) at depth
+// T, into the int32x4 pixel.  `reflectivity` is read at the slots of levels
+// below max_bounces only.
+template <typename W>
+RT_LIGHT_FN void lit_chain_from(const rt_scene& s, Vec3 p, Vec3 n, Vec3 D, int32_t obj, float T,
+                                const float* reflectivity, int32_t max_bounces, bool shadows,
+                                int32_t out[4], const W& w) {
     Vec3 a[RT_MAX_BOUNCES];  // the levels the chain went on from
     float r[RT_MAX_BOUNCES];
     Vec3 C{0.0f, 0.0f, 0.0f};
@@ -721,11 +736,7 @@ RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float*
             ++j;
             break;
         }
-        const Vec3 p2 = bounce_point(p, R, b.best);
-        n = bounce_normal(s, b.obj2, b.tri2, p2, R);
-        p = p2;
-        obj = b.obj2;
-        D = R;
+        next_level(s, b, R, p, n, D, obj);
         T = T + b.best;
     }
     for (int32_t l = j - 1; l >= 0; --l) C = chain_blend(a[l], r[l], C);
@@ -733,6 +744,27 @@ RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float*
     out[1] = cvt_i32(C.y);
     out[2] = cvt_i32(C.z);
     out[3] = 255;
+}
+
+// One pixel of the mirrored frame (int32x4): the chain from the hit frame's
+// level 0.  A miss, and t == kFar, are lit_pixel's (with `shadows`,
+// lit_pixel_shadowed's).
+template <typename W = Walks>
+RT_LIGHT_FN void lit_pixel_mirrored(const rt_scene& s, int32_t obj, const float* verts, float ox,
+                                    float oy, Vec3 d, float t, const float* reflectivity,
+                                    int32_t max_bounces, bool shadows, int32_t out[4],
+                                    const W& w = W()) {
+    if (obj < 0 || t == kFar) {
+        if (shadows)
+            lit_pixel_shadowed(s, obj, verts, ox, oy, d, t, out, w);
+        else
+            lit_pixel(s, obj, verts, ox, oy, d, t, out);
+        return;
+    }
+    const Vec3 p = hit_point(ox, oy, d, t);
+    const rt_surface sf = surface(s, obj, verts, ox, oy, d, t, p);
+    lit_chain_from(s, p, Vec3{sf.nx, sf.ny, sf.nz}, d, obj, t, reflectivity, max_bounces, shadows,
+                   out, w);
 }
 
 }  // namespace rt_light

@@ -601,19 +601,42 @@ def _hit_band(hits: np.ndarray, rows: Optional[Tuple[int, int]]):
     return hits, rb, re
 
 
+def _per_hit(call: str, hits: np.ndarray, scene: Scene, cull: tuple, rows, ray_dir, out, *own):
+    """A host call of the light pass over a "hit" frame: library().<call>(hits,
+    scene, *cull, ray_dir, width, row_begin, row_end, *own, out).  `out`: the
+    dtype of one output per pixel, in the hits' shape, or the format name of a
+    lit frame, whose code then follows `own`."""
+    hits, rb, re = _hit_band(hits, rows)
+    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+    if isinstance(out, str):
+        own += (_FORMATS[out],)
+        out = np.empty(*_frame_layout(out, re - rb, hits.shape[1]))
+    else:
+        out = np.empty(hits.shape, out)
+    sc = scene.as_c()
+    _check(getattr(library(), call)(_ptr(hits), ctypes.byref(sc), *cull, _ptr(d), hits.shape[1],
+                                    rb, re, *own, _ptr(out)), call)
+    return out
+
+
+def _reflectivity(reflectivity, scene: Scene) -> Optional[np.ndarray]:
+    """One float32 per colour slot of `scene`, or None."""
+    if reflectivity is None:
+        return None
+    refl = np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
+    if refl.size != scene.num_cubes + scene.num_spheres:
+        raise ValueError(f"reflectivity must hold one value per colour slot "
+                         f"({scene.num_cubes + scene.num_spheres}), got {refl.size}")
+    return refl
+
+
 def hit_surfaces(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
                  ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
     """rt_hit_surfaces: per pixel of a "hit" frame (rows x width HIT_DTYPE;
     `rows` = the band of the frame it holds, default from row 0) the unit
     normal turned against the ray and the cube triangle that was hit, as a
     SURFACE_DTYPE array of the same shape.  On the host."""
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(hits.shape, SURFACE_DTYPE)
-    sc = scene.as_c()
-    _check(library().rt_hit_surfaces(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
-                                     _ptr(out)), "rt_hit_surfaces")
-    return out
+    return _per_hit("rt_hit_surfaces", hits, scene, (), rows, ray_dir, SURFACE_DTYPE)
 
 
 def light_hits(hits: np.ndarray, scene: Scene, fmt: str = "i32x4",
@@ -626,15 +649,8 @@ def light_hits(hits: np.ndarray, scene: Scene, fmt: str = "i32x4",
     nothing.  On the host."""
     if fmt not in ("i32x4", "rgba8"):
         raise ValueError("light_hits gives an i32x4 or an rgba8 frame")
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
-    sc = scene.as_c()
-    fn, name = ((library().rt_light_hits_shadowed, "rt_light_hits_shadowed") if shadows
-                else (library().rt_light_hits, "rt_light_hits"))
-    _check(fn(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re, _FORMATS[fmt],
-              _ptr(out)), name)
-    return out
+    return _per_hit("rt_light_hits_shadowed" if shadows else "rt_light_hits", hits, scene, (),
+                    rows, ray_dir, fmt)
 
 
 def shadow_hits(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
@@ -642,13 +658,7 @@ def shadow_hits(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] 
     """rt_shadow_hits: per pixel of a "hit" frame a uint32 whose bit i is set
     iff light i of `scene.lights` faces the hit point and another object of
     the scene hides it (at most 32 lights).  On the host."""
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(hits.shape, np.uint32)
-    sc = scene.as_c()
-    _check(library().rt_shadow_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
-                                    _ptr(out)), "rt_shadow_hits")
-    return out
+    return _per_hit("rt_shadow_hits", hits, scene, (), rows, ray_dir, np.uint32)
 
 
 def reflect_hits(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
@@ -658,13 +668,7 @@ def reflect_hits(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]]
     HIT_DTYPE array of the same shape: the parameter along the (un-normalised)
     mirrored direction and the colour slot; (HIT_MISS_T, -1) where the bounce
     meets nothing or the pixel is a miss.  On the host."""
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(hits.shape, HIT_DTYPE)
-    sc = scene.as_c()
-    _check(library().rt_reflect_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
-                                     _ptr(out)), "rt_reflect_hits")
-    return out
+    return _per_hit("rt_reflect_hits", hits, scene, (), rows, ray_dir, HIT_DTYPE)
 
 
 def light_hits_reflected(hits: np.ndarray, scene: Scene, reflectivity: float,
@@ -676,14 +680,7 @@ def light_hits_reflected(hits: np.ndarray, scene: Scene, reflectivity: float,
     for bit.  On the host."""
     if fmt not in ("i32x4", "rgba8"):
         raise ValueError("light_hits_reflected gives an i32x4 or an rgba8 frame")
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
-    sc = scene.as_c()
-    _check(library().rt_light_hits_reflected(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1],
-                                             rb, re, reflectivity, _FORMATS[fmt], _ptr(out)),
-           "rt_light_hits_reflected")
-    return out
+    return _per_hit("rt_light_hits_reflected", hits, scene, (), rows, ray_dir, fmt, reflectivity)
 
 
 def light_hits_shadowed_reflected(hits: np.ndarray, scene: Scene, reflectivity: float,
@@ -696,14 +693,8 @@ def light_hits_shadowed_reflected(hits: np.ndarray, scene: Scene, reflectivity: 
     light_hits(shadows=True)'s frame bit for bit.  On the host."""
     if fmt not in ("i32x4", "rgba8"):
         raise ValueError("light_hits_shadowed_reflected gives an i32x4 or an rgba8 frame")
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
-    sc = scene.as_c()
-    _check(library().rt_light_hits_shadowed_reflected(
-        _ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re, reflectivity, _FORMATS[fmt],
-        _ptr(out)), "rt_light_hits_shadowed_reflected")
-    return out
+    return _per_hit("rt_light_hits_shadowed_reflected", hits, scene, (), rows, ray_dir, fmt,
+                    reflectivity)
 
 
 def shadow_hits_reflected(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[int, int]] = None,
@@ -712,14 +703,7 @@ def shadow_hits_reflected(hits: np.ndarray, scene: Scene, rows: Optional[Tuple[i
     pixel mirrors: bit i is set iff light i faces that point and an object
     other than the mirrored one hides it (at most 32 lights); 0 where the
     pixel mirrors nothing.  On the host."""
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(hits.shape, np.uint32)
-    sc = scene.as_c()
-    _check(library().rt_shadow_hits_reflected(_ptr(hits), ctypes.byref(sc), _ptr(d),
-                                              hits.shape[1], rb, re, _ptr(out)),
-           "rt_shadow_hits_reflected")
-    return out
+    return _per_hit("rt_shadow_hits_reflected", hits, scene, (), rows, ray_dir, np.uint32)
 
 
 def bounce_hits(hits: np.ndarray, scene: Scene, bounce: int,
@@ -731,13 +715,7 @@ def bounce_hits(hits: np.ndarray, scene: Scene, bounce: int,
     (the parameter along that bounce's direction, the colour slot met);
     (HIT_MISS_T, -1) where this bounce or an earlier one meets nothing.
     bounce=1 is reflect_hits' frame.  On the host."""
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(hits.shape, HIT_DTYPE)
-    sc = scene.as_c()
-    _check(library().rt_bounce_hits(_ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re,
-                                    int(bounce), _ptr(out)), "rt_bounce_hits")
-    return out
+    return _per_hit("rt_bounce_hits", hits, scene, (), rows, ray_dir, HIT_DTYPE, int(bounce))
 
 
 def light_hits_mirrored(hits: np.ndarray, scene: Scene, reflectivity, max_bounces: int,
@@ -754,20 +732,9 @@ def light_hits_mirrored(hits: np.ndarray, scene: Scene, reflectivity, max_bounce
     (light_hits_shadowed_reflected's) frame bit for bit.  On the host."""
     if fmt not in ("i32x4", "rgba8"):
         raise ValueError("light_hits_mirrored gives an i32x4 or an rgba8 frame")
-    hits, rb, re = _hit_band(hits, rows)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    refl = None
-    if reflectivity is not None:
-        refl = np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
-        if refl.size != scene.num_cubes + scene.num_spheres:
-            raise ValueError(f"reflectivity must hold one value per colour slot "
-                             f"({scene.num_cubes + scene.num_spheres}), got {refl.size}")
-    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
-    sc = scene.as_c()
-    _check(library().rt_light_hits_mirrored(
-        _ptr(hits), ctypes.byref(sc), _ptr(d), hits.shape[1], rb, re, _ptr(refl),
-        int(max_bounces), int(shadows), _FORMATS[fmt], _ptr(out)), "rt_light_hits_mirrored")
-    return out
+    refl = _reflectivity(reflectivity, scene)
+    return _per_hit("rt_light_hits_mirrored", hits, scene, (), rows, ray_dir, fmt, _ptr(refl),
+                    int(max_bounces), int(shadows))
 
 
 def _vec3(v) -> np.ndarray:
@@ -1019,15 +986,8 @@ def shadow_hits_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray,
                       ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
     """rt_shadow_hits_accel: shadow_hits' mask word for word, the shadow
     segments culled by `accel` (build_accel(scene)).  On the host."""
-    hits, rb, re = _hit_band(hits, rows)
     accel = _accel(accel, scene)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(hits.shape, np.uint32)
-    sc = scene.as_c()
-    _check(library().rt_shadow_hits_accel(_ptr(hits), ctypes.byref(sc), _ptr(accel), _ptr(d),
-                                          hits.shape[1], rb, re, _ptr(out)),
-           "rt_shadow_hits_accel")
-    return out
+    return _per_hit("rt_shadow_hits_accel", hits, scene, (_ptr(accel),), rows, ray_dir, np.uint32)
 
 
 def bounce_hits_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray, bounce: int,
@@ -1035,15 +995,9 @@ def bounce_hits_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray, bounce:
                       ray_dir: Optional[np.ndarray] = None) -> np.ndarray:
     """rt_bounce_hits_accel: bounce_hits' frame word for word, every bounce
     culled by `accel` (build_accel(scene)).  On the host."""
-    hits, rb, re = _hit_band(hits, rows)
     accel = _accel(accel, scene)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    out = np.empty(hits.shape, HIT_DTYPE)
-    sc = scene.as_c()
-    _check(library().rt_bounce_hits_accel(_ptr(hits), ctypes.byref(sc), _ptr(accel), _ptr(d),
-                                          hits.shape[1], rb, re, int(bounce), _ptr(out)),
-           "rt_bounce_hits_accel")
-    return out
+    return _per_hit("rt_bounce_hits_accel", hits, scene, (_ptr(accel),), rows, ray_dir, HIT_DTYPE,
+                    int(bounce))
 
 
 def light_hits_mirrored_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray, reflectivity,
@@ -1056,21 +1010,9 @@ def light_hits_mirrored_accel(hits: np.ndarray, scene: Scene, accel: np.ndarray,
     light_hits(shadows=True)'s frame.  On the host."""
     if fmt not in ("i32x4", "rgba8"):
         raise ValueError("light_hits_mirrored_accel gives an i32x4 or an rgba8 frame")
-    hits, rb, re = _hit_band(hits, rows)
-    accel = _accel(accel, scene)
-    d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-    refl = None
-    if reflectivity is not None:
-        refl = np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
-        if refl.size != scene.num_cubes + scene.num_spheres:
-            raise ValueError(f"reflectivity must hold one value per colour slot "
-                             f"({scene.num_cubes + scene.num_spheres}), got {refl.size}")
-    out = np.empty(*_frame_layout(fmt, re - rb, hits.shape[1]))
-    sc = scene.as_c()
-    _check(library().rt_light_hits_mirrored_accel(
-        _ptr(hits), ctypes.byref(sc), _ptr(accel), _ptr(d), hits.shape[1], rb, re, _ptr(refl),
-        int(max_bounces), int(shadows), _FORMATS[fmt], _ptr(out)), "rt_light_hits_mirrored_accel")
-    return out
+    accel, refl = _accel(accel, scene), _reflectivity(reflectivity, scene)
+    return _per_hit("rt_light_hits_mirrored_accel", hits, scene, (_ptr(accel),), rows, ray_dir,
+                    fmt, _ptr(refl), int(max_bounces), int(shadows))
 
 
 def light_camera(camera: Camera, scene: Scene, width: int, height: int, reflectivity=None,
@@ -1089,12 +1031,7 @@ def light_camera(camera: Camera, scene: Scene, width: int, height: int, reflecti
     if accel is not None:
         accel = _accel(accel, scene)
     rb, re = rows if rows is not None else (0, height)
-    refl = None
-    if reflectivity is not None:
-        refl = np.ascontiguousarray(reflectivity, np.float32).reshape(-1)
-        if refl.size != scene.num_cubes + scene.num_spheres:
-            raise ValueError(f"reflectivity must hold one value per colour slot "
-                             f"({scene.num_cubes + scene.num_spheres}), got {refl.size}")
+    refl = _reflectivity(reflectivity, scene)
     out = np.empty(*_frame_layout(fmt, max(re - rb, 0), max(width, 0)))
     c, sc = camera.as_c(), scene.as_c()
     _check(library().rt_light_camera(
@@ -1212,6 +1149,17 @@ class RayTracer:
                                           _FORMATS[fmt], _PATHS[path], out_ptr, stream or None),
                "rt_render_device")
 
+    def _hits_device(self, call: str, hits_ptr: int, device_scene: dict, cull: tuple, width: int,
+                     rows: Tuple[int, int], ray_dir, out_ptr: int, stream: int, *own) -> None:
+        """A device call of the light pass over a hit frame: library().<call>(
+        ctx, hits, scene, *cull, ray_dir, width, row_begin, row_end, *own, out,
+        stream), a 0 address as NULL."""
+        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
+        sc = _device_scene(device_scene)
+        _check(getattr(library(), call)(self._ctx, hits_ptr or None, ctypes.byref(sc),
+                                        *[c or None for c in cull], _ptr(d), width, rows[0],
+                                        rows[1], *own, out_ptr or None, stream or None), call)
+
     def hit_surfaces_device(self, hits_ptr: int, device_scene: dict, width: int,
                             rows: Tuple[int, int], out_ptr: int,
                             ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
@@ -1219,12 +1167,8 @@ class RayTracer:
         frame at `hits_ptr` to rt_surface records at `out_ptr` (16-byte
         aligned).  Asynchronous on `stream`.  `device_scene` as for
         render_device."""
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_hit_surfaces_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
-                                                _ptr(d), width, rows[0], rows[1],
-                                                out_ptr or None, stream or None),
-               "rt_hit_surfaces_device")
+        self._hits_device("rt_hit_surfaces_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream)
 
     def light_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
                           rows: Tuple[int, int], out_ptr: int,
@@ -1236,36 +1180,25 @@ class RayTracer:
         shadows=True: rt_light_hits_shadowed_device.  Asynchronous on `stream`."""
         if fmt not in ("i32x4", "rgba8"):
             raise ValueError("light_hits_device gives an i32x4 or an rgba8 frame")
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        fn, name = ((library().rt_light_hits_shadowed_device, "rt_light_hits_shadowed_device")
-                    if shadows else (library().rt_light_hits_device, "rt_light_hits_device"))
-        _check(fn(self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
-                  _FORMATS[fmt], out_ptr or None, stream or None), name)
+        self._hits_device("rt_light_hits_shadowed_device" if shadows else "rt_light_hits_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream,
+                          _FORMATS[fmt])
 
     def shadow_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
                            rows: Tuple[int, int], out_ptr: int,
                            ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
         """rt_shadow_hits_device: a device hit frame to one uint32 shadow mask
         per pixel at `out_ptr` (at most 32 lights).  Asynchronous on `stream`."""
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_shadow_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
-                                               _ptr(d), width, rows[0], rows[1],
-                                               out_ptr or None, stream or None),
-               "rt_shadow_hits_device")
+        self._hits_device("rt_shadow_hits_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream)
 
     def reflect_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
                             rows: Tuple[int, int], out_ptr: int,
                             ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
         """rt_reflect_hits_device: a device hit frame to the hit frame of its
         mirror bounce at `out_ptr` (8-byte aligned).  Asynchronous on `stream`."""
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_reflect_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
-                                                _ptr(d), width, rows[0], rows[1],
-                                                out_ptr or None, stream or None),
-               "rt_reflect_hits_device")
+        self._hits_device("rt_reflect_hits_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream)
 
     def light_hits_reflected_device(self, hits_ptr: int, device_scene: dict, width: int,
                                     rows: Tuple[int, int], out_ptr: int, reflectivity: float,
@@ -1278,14 +1211,10 @@ class RayTracer:
         point and at the mirrored point.  Asynchronous on `stream`."""
         if fmt not in ("i32x4", "rgba8"):
             raise ValueError("light_hits_reflected_device gives an i32x4 or an rgba8 frame")
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        fn, name = ((library().rt_light_hits_shadowed_reflected_device,
-                     "rt_light_hits_shadowed_reflected_device") if shadows
-                    else (library().rt_light_hits_reflected_device,
-                          "rt_light_hits_reflected_device"))
-        _check(fn(self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
-                  reflectivity, _FORMATS[fmt], out_ptr or None, stream or None), name)
+        self._hits_device("rt_light_hits_shadowed_reflected_device" if shadows
+                          else "rt_light_hits_reflected_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream,
+                          reflectivity, _FORMATS[fmt])
 
     def shadow_hits_reflected_device(self, hits_ptr: int, device_scene: dict, width: int,
                                      rows: Tuple[int, int], out_ptr: int,
@@ -1294,11 +1223,8 @@ class RayTracer:
         """rt_shadow_hits_reflected_device: a device hit frame to one uint32
         shadow mask per pixel at `out_ptr`, taken at the point the pixel
         mirrors (at most 32 lights).  Asynchronous on `stream`."""
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_shadow_hits_reflected_device(
-            self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
-            out_ptr or None, stream or None), "rt_shadow_hits_reflected_device")
+        self._hits_device("rt_shadow_hits_reflected_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream)
 
     def bounce_hits_device(self, hits_ptr: int, device_scene: dict, width: int,
                            rows: Tuple[int, int], out_ptr: int, bounce: int,
@@ -1306,12 +1232,9 @@ class RayTracer:
         """rt_bounce_hits_device: a device hit frame to the hit frame of bounce
         number `bounce` (1 .. RT_MAX_BOUNCES) of its mirror chains at `out_ptr`
         (8-byte aligned).  Asynchronous on `stream`."""
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_bounce_hits_device(self._ctx, hits_ptr or None, ctypes.byref(sc),
-                                               _ptr(d), width, rows[0], rows[1], int(bounce),
-                                               out_ptr or None, stream or None),
-               "rt_bounce_hits_device")
+        self._hits_device("rt_bounce_hits_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream,
+                          int(bounce))
 
     def light_hits_mirrored_device(self, hits_ptr: int, device_scene: dict, width: int,
                                    rows: Tuple[int, int], out_ptr: int, reflectivity_ptr: int,
@@ -1326,12 +1249,9 @@ class RayTracer:
         asynchronous on `stream`."""
         if fmt not in ("i32x4", "rgba8"):
             raise ValueError("light_hits_mirrored_device gives an i32x4 or an rgba8 frame")
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_light_hits_mirrored_device(
-            self._ctx, hits_ptr or None, ctypes.byref(sc), _ptr(d), width, rows[0], rows[1],
-            reflectivity_ptr or None, int(max_bounces), int(shadows), _FORMATS[fmt],
-            out_ptr or None, stream or None), "rt_light_hits_mirrored_device")
+        self._hits_device("rt_light_hits_mirrored_device",
+                          hits_ptr, device_scene, (), width, rows, ray_dir, out_ptr, stream,
+                          reflectivity_ptr or None, int(max_bounces), int(shadows), _FORMATS[fmt])
 
     def cast_rays_device(self, rays_ptr: int, n: int, device_scene: dict, hits_ptr: int,
                          triangles_ptr: int = 0, stream: int = 0) -> None:
@@ -1467,23 +1387,18 @@ class RayTracer:
         """rt_shadow_hits_accel_device: shadow_hits_device culled by the
         records at `accel_ptr` (build_accel_device's, of this scene).
         Asynchronous on `stream`."""
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_shadow_hits_accel_device(
-            self._ctx, hits_ptr or None, ctypes.byref(sc), accel_ptr or None, _ptr(d), width,
-            rows[0], rows[1], out_ptr or None, stream or None), "rt_shadow_hits_accel_device")
+        self._hits_device("rt_shadow_hits_accel_device",
+                          hits_ptr, device_scene, (accel_ptr,), width, rows, ray_dir, out_ptr,
+                          stream)
 
     def bounce_hits_accel_device(self, hits_ptr: int, device_scene: dict, accel_ptr: int,
                                  width: int, rows: Tuple[int, int], out_ptr: int, bounce: int,
                                  ray_dir: Optional[np.ndarray] = None, stream: int = 0) -> None:
         """rt_bounce_hits_accel_device: bounce_hits_device culled by the
         records at `accel_ptr`.  Asynchronous on `stream`."""
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_bounce_hits_accel_device(
-            self._ctx, hits_ptr or None, ctypes.byref(sc), accel_ptr or None, _ptr(d), width,
-            rows[0], rows[1], int(bounce), out_ptr or None, stream or None),
-            "rt_bounce_hits_accel_device")
+        self._hits_device("rt_bounce_hits_accel_device",
+                          hits_ptr, device_scene, (accel_ptr,), width, rows, ray_dir, out_ptr,
+                          stream, int(bounce))
 
     def light_hits_mirrored_accel_device(self, hits_ptr: int, device_scene: dict, accel_ptr: int,
                                          width: int, rows: Tuple[int, int], out_ptr: int,
@@ -1495,13 +1410,10 @@ class RayTracer:
         `stream`."""
         if fmt not in ("i32x4", "rgba8"):
             raise ValueError("light_hits_mirrored_accel_device gives an i32x4 or an rgba8 frame")
-        d = primary_ray_dir() if ray_dir is None else np.ascontiguousarray(ray_dir, np.float32)
-        sc = _device_scene(device_scene)
-        _check(library().rt_light_hits_mirrored_accel_device(
-            self._ctx, hits_ptr or None, ctypes.byref(sc), accel_ptr or None, _ptr(d), width,
-            rows[0], rows[1], reflectivity_ptr or None, int(max_bounces), int(shadows),
-            _FORMATS[fmt], out_ptr or None, stream or None),
-            "rt_light_hits_mirrored_accel_device")
+        self._hits_device("rt_light_hits_mirrored_accel_device",
+                          hits_ptr, device_scene, (accel_ptr,), width, rows, ray_dir, out_ptr,
+                          stream, reflectivity_ptr or None, int(max_bounces), int(shadows),
+                          _FORMATS[fmt])
 
     def light_camera_device(self, camera: Camera, device_scene: dict, accel_ptr: int, width: int,
                             rows: Tuple[int, int], refl_ptr: int, max_bounces: int,

@@ -3,10 +3,8 @@
 // checks they share with rt_camera_light.hip.  One pixel loop over the pixel
 // functions of include/rt_camera_light_impl.h, which take the unculled walks
 // (accel == NULL) or the culled ones.  rt_light_run.h's loop reads a hit frame,
-// which these calls do not have; its Lit and its store are used as they are.
+// which these calls do not have; its Lit and its store_pixel are used as they are.
 // Plain C++, no HIP; built with -ffp-contract=off like rt_light.cpp.
-#include <cstring>
-
 #include "rt_camera_light_impl.h"
 #include "rt_hip.h"
 #include "rt_light_run.h"
@@ -23,37 +21,18 @@ int check_camera_light(const rt_camera* camera, const rt_scene* scene, const rt_
     return RT_OK;
 }
 
-int check_camera_lit(const rt_scene* scene, const float* reflectivity, int32_t max_bounces,
-                     int32_t shadows, int32_t out_format) {
-    if (out_format != RT_FORMAT_I32X4 && out_format != RT_FORMAT_RGBA8) return RT_ERR_INVALID_ARG;
-    if (max_bounces < 0 || max_bounces > RT_MAX_BOUNCES) return RT_ERR_INVALID_ARG;
-    if (shadows != 0 && shadows != 1) return RT_ERR_INVALID_ARG;
-    // (the counts are checked by check_camera_light; a scene it refuses is never read)
-    if (!reflectivity && max_bounces > 0 && scene &&
-        static_cast<int64_t>(scene->num_cubes) + scene->num_spheres > 0)
-        return RT_ERR_INVALID_ARG;
-    return RT_OK;
-}
-
 namespace {
 
 // The pixel loop of both calls: `pixel(ray)` per pixel of the band, row-major;
-// a Lit is stored in `fmt`, an rt_hit as it is.
+// what it returns is stored by store_pixel.
 template <typename PixelFn>
 void run_camera(const rt_camera& cam, int32_t width, int32_t row_begin, int32_t row_end,
                 int32_t fmt, void* out, PixelFn pixel) {
     int64_t i = 0;
     for (int32_t y = row_begin; y < row_end; ++y)
-        for (int32_t x = 0; x < width; ++x, ++i) {
-            const auto v = pixel(camera_ray(cam, static_cast<float>(x), static_cast<float>(y)));
-            using Out = std::remove_const_t<decltype(v)>;
-            if constexpr (!std::is_same_v<Out, Lit>)
-                static_cast<Out*>(out)[i] = v;
-            else if (fmt == RT_FORMAT_I32X4)
-                std::memcpy(static_cast<int32_t*>(out) + 4 * i, v.p, sizeof v.p);
-            else
-                static_cast<uint32_t*>(out)[i] = pack_rgba8(v.p);
-        }
+        for (int32_t x = 0; x < width; ++x, ++i)
+            store_pixel(out, i, fmt,
+                        pixel(camera_ray(cam, static_cast<float>(x), static_cast<float>(y))));
 }
 
 template <typename W>
@@ -100,15 +79,13 @@ int rt_bounce_camera(const rt_camera* camera, const rt_scene* scene, const rt_cu
 int rt_light_camera(const rt_camera* camera, const rt_scene* scene, const rt_cube_bound* accel,
                     int32_t width, int32_t row_begin, int32_t row_end, const float* reflectivity,
                     int32_t max_bounces, int32_t shadows, int32_t out_format, void* out) {
-    int rc = check_camera_lit(scene, reflectivity, max_bounces, shadows, out_format);
+    int rc = check_chain_settings(scene, reflectivity, max_bounces, shadows, out_format);
     if (!rc)
         rc = check_camera_light(camera, scene, accel, width, row_begin, row_end, out,
                                 out_format == RT_FORMAT_I32X4 ? 16 : 4);
+    bool mirrors = false;
+    if (!rc) rc = check_reflectivity(*scene, reflectivity, mirrors);
     if (rc) return rc;
-    const int64_t n_slots = static_cast<int64_t>(scene->num_cubes) + scene->num_spheres;
-    if (reflectivity)
-        for (int64_t i = 0; i < n_slots; ++i)
-            if (!(reflectivity[i] >= 0.0f && reflectivity[i] <= 1.0f)) return RT_ERR_INVALID_ARG;
     // without an array no slot can be read (an empty scene): depth 0
     const int32_t depth = reflectivity ? max_bounces : 0;
     if (accel)

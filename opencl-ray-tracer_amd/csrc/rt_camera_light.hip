@@ -6,13 +6,16 @@
 // frame, no workspace, and no fp64 re-identification of the level-0 triangle.
 //
 // One kernel template over the output (int32x4, RGBA8, bounce frame) and over
-// the walks of rt_light_device.inc (unculled, or culled by CubeCull of
+// the cull policy of the walks of rt_light_device.inc (KeepAll, or CubeCull of
 // rt_accel_impl.h on the prebuilt records).  One pixel per lane in 256-thread
-// workgroups.  The ballots, the LDS blend stack (depth * 4 KiB of dynamic shared memory; none for the
-// bounce frame) and the unwind are rt_light_accel.hip's, restated so that that
-// file and its kernels stay as they are.
-//
-// The level loop is entered one step early: the camera ray is the "bounce"
+// workgroups.  The level a bounce reaches, the chain's pixel and the entry
+// points' preamble are rt_chain_device.inc's and rt_light_impl.h's.  The level
+// loop, with the level step, the LDS blend stack (depth * 4 KiB of dynamic
+// shared memory; none for the bounce frame) and the unwind, is written here a
+// second time, beside hit_chain_kernel's: its shape differs, and with the level
+// step and the unwind as functions of both kernels the culled instances were
+// up to 1.4 % slower (profiles/chain_shared/README.md).  The shape:
+// the level loop is entered one step early: the camera ray is the "bounce"
 // that reaches level 0, from own object -1, so the kernel has the two walk
 // sites of light_accel_kernel (one closest-hit walk, one shadow walk) and not a
 // third copy of the walk in front of the loop.  These kernels are short of
@@ -32,33 +35,29 @@
 #define RT_ACCEL_NORMALS_LOOP _Pragma("clang loop unroll(disable)")
 #endif
 #include "rt_accel_impl.h"
-#include "rt_rays_device.inc"  // camera_ray_at
+#include "rt_chain_device.inc"
+#include "rt_rays_device.inc"  // camera_ray_at, launch_rays
 #include "rt_camera_light_impl.h"
 
 namespace {
 
 using rt_light::CubeCull;
 
-enum { kOutBounce = 2 };
-
-// The closest-hit walk of the instance, for the lanes that cast.
-template <bool kCulled>
-__device__ __forceinline__ rt_light::Bounce walk(const rt_scene& s,
-                                                 const rt_cube_bound* __restrict__ accel,
-                                                 rt_light::Vec3 p, rt_light::Vec3 R, int32_t own,
-                                                 bool casts) {
-    if constexpr (kCulled)
-        return wave_bounce_walk(s, p, R, own, casts, CubeCull{accel});
+// The policy of an instance over the kernel's `accel` argument.
+template <typename Cull>
+__device__ __forceinline__ Cull policy(const rt_cube_bound* accel) {
+    if constexpr (std::is_same_v<Cull, CubeCull>)
+        return CubeCull{accel};
     else
-        return wave_bounce_walk(s, p, R, own, casts);
+        return KeepAll{};
 }
 
-// `s` holds device pointers, `accel` its s.num_cubes records (kCulled only).
+// `s` holds device pointers, `accel` its s.num_cubes records (CubeCull only).
 // `depth`: max_bounces of the lit forms (0 .. RT_MAX_BOUNCES; the launch passes
 // depth * 4 KiB of shared memory), the bounce's number of the bounce form
 // (0 .. RT_MAX_BOUNCES).  `refl`: the lit forms' reflectivity by colour slot.
 // (uniform: depth, shadows)
-template <int kOut, bool kCulled>
+template <int kOut, typename Cull>
 __global__ void __launch_bounds__(256)
 camera_light_kernel(rt_camera cam, int64_t n, int32_t width, int32_t row_begin,
                     const rt_cube_bound* __restrict__ accel, const float* __restrict__ refl,
@@ -81,17 +80,18 @@ camera_light_kernel(rt_camera cam, int64_t n, int32_t width, int32_t row_begin,
     // for level 0 the camera ray, from no object
     Vec3 p = ray.o, R = ray.d, nrm{0.0f, 0.0f, 0.0f};
     int32_t cur = -1;
+    const Cull cull = policy<Cull>(accel);
 
     if constexpr (kOut == kOutBounce) {
         rt_light::Bounce b{rt_light::kFar, -1, -1};
         bool live = in;  // the lane casts the next walk
 #pragma clang loop unroll(disable)
         for (int32_t j = 0;; ++j) {  // (uniform)
-            b = walk<kCulled>(s, accel, p, R, cur, live);  // (kFar, -1) for the others
-            if (j >= depth) break;                         // (uniform)
+            b = wave_bounce_walk(s, p, R, cur, live, cull);  // (kFar, -1) for the others
+            if (j >= depth) break;                           // (uniform)
             live = b.obj2 >= 0;
             if (__ballot(live) == 0) break;  // (uniform)
-            if (live) rt_light::camera_next_level(s, b, R, p, nrm, cur);
+            if (live) rt_light::next_level(s, b, R, p, nrm, cur);
             R = rt_light::mirror_dir(nrm, R);
         }
         if (dst) *reinterpret_cast<int2*>(dst) = make_int2(__float_as_int(b.best), b.obj2);
@@ -111,22 +111,19 @@ camera_light_kernel(rt_camera cam, int64_t n, int32_t width, int32_t row_begin,
         int32_t j = 0;
 #pragma clang loop unroll(disable)
         for (;; ++j) {
-            const rt_light::Bounce b = walk<kCulled>(s, accel, p, R, cur, goes);
+            const rt_light::Bounce b = wave_bounce_walk(s, p, R, cur, goes, cull);
             const bool live = goes && b.obj2 >= 0;  // a miss leaves C = (0, 0, 0)
             if (__ballot(live) == 0) break;         // (uniform)
             if (live) {
                 T = j == 0 ? b.best : T + b.best;
-                rt_light::camera_next_level(s, b, R, p, nrm, cur);
+                rt_light::next_level(s, b, R, p, nrm, cur);
             }
             // the own colour of level j, for the lanes that reached it
             float k = 1.0f;
             if (lights) {       // (uniform)
                 if (shadows) {  // (uniform)
                     uint32_t unused = 0;
-                    if constexpr (kCulled)
-                        k = light_walk<false>(s, p, nrm, cur, live, unused, CubeCull{accel});
-                    else
-                        k = light_walk<false>(s, p, nrm, cur, live, unused);
+                    k = light_walk<false>(s, p, nrm, cur, live, unused, cull);
                 } else if (live) {
                     k = rt_light::light_factor(nrm, p, s.lights, s.num_lights);
                 }
@@ -157,8 +154,8 @@ camera_light_kernel(rt_camera cam, int64_t n, int32_t width, int32_t row_begin,
             }
         }
         if (dst) {
-            const int32_t lit[4] = {rt_light::cvt_i32(C.x), rt_light::cvt_i32(C.y),
-                                    rt_light::cvt_i32(C.z), 255};
+            int32_t lit[4];
+            chain_lit(C, lit);
             store_lit<kOut>(dst, 0, lit);
         }
     }
@@ -177,14 +174,11 @@ int launch_camera(Kernel unculled, Kernel culled, uintptr_t align, rt_ctx* ctx,
     if (rc) return rc;
     // (n >= 1: the checks refuse an empty band; blocks <= INT32_MAX: and more pixels than that)
     const int64_t n = (int64_t)(row_end - row_begin) * width;
-    const int64_t blocks = (n + 255) / 256;
-    if (hipSetDevice(rt_internal::ctx_device(ctx)) != hipSuccess) return RT_ERR_HIP;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : rt_internal::ctx_stream(ctx);
-    if (!st) return RT_ERR_HIP;
     const Kernel kernel = accel ? culled : unculled;  // NULL accel: every walk unculled
-    kernel<<<dim3((unsigned)blocks), dim3(256), shared, st>>>(
-        *camera, n, width, row_begin, accel, refl, depth, shadows, *scene, out);
-    return hipGetLastError() == hipSuccess ? RT_OK : RT_ERR_HIP;
+    return launch_rays(ctx, n, 256, stream, [&](dim3 grid, hipStream_t st) {
+        kernel<<<grid, dim3(256), shared, st>>>(*camera, n, width, row_begin, accel, refl, depth,
+                                                shadows, *scene, out);
+    });
 }
 
 }  // namespace
@@ -195,8 +189,8 @@ int rt_bounce_camera_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene
                             const rt_cube_bound* device_accel, int32_t width, int32_t row_begin,
                             int32_t row_end, int32_t bounce, rt_hit* device_out, void* stream) {
     if (bounce < 0 || bounce > RT_MAX_BOUNCES) return RT_ERR_INVALID_ARG;
-    return launch_camera(camera_light_kernel<kOutBounce, false>,
-                         camera_light_kernel<kOutBounce, true>, 8, ctx, camera, device_scene,
+    return launch_camera(camera_light_kernel<kOutBounce, KeepAll>,
+                         camera_light_kernel<kOutBounce, CubeCull>, 8, ctx, camera, device_scene,
                          device_accel, width, row_begin, row_end, nullptr, bounce, 0, 0,
                          device_out, stream);
 }
@@ -205,19 +199,18 @@ int rt_light_camera_device(rt_ctx* ctx, const rt_camera* camera, const rt_scene*
                            const rt_cube_bound* device_accel, int32_t width, int32_t row_begin,
                            int32_t row_end, const float* device_reflectivity, int32_t max_bounces,
                            int32_t shadows, int32_t out_format, void* device_out, void* stream) {
-    const int rc = rt_light::check_camera_lit(device_scene, device_reflectivity, max_bounces,
-                                              shadows, out_format);
+    int32_t depth;
+    size_t shared;
+    const int rc = chain_settings(device_scene, device_reflectivity, max_bounces, shadows,
+                                  out_format, depth, shared);
     if (rc) return rc;
-    // without an array no slot can be read: the kernel then runs at depth 0
-    const int32_t depth = device_reflectivity ? max_bounces : 0;
-    const size_t shared = 256 * sizeof(float4) * (size_t)depth;
     if (out_format == RT_FORMAT_I32X4)
-        return launch_camera(camera_light_kernel<kOutI32x4, false>,
-                             camera_light_kernel<kOutI32x4, true>, 16, ctx, camera, device_scene,
-                             device_accel, width, row_begin, row_end, device_reflectivity, depth,
-                             shadows, shared, device_out, stream);
-    return launch_camera(camera_light_kernel<kOutRgba8, false>,
-                         camera_light_kernel<kOutRgba8, true>, 4, ctx, camera, device_scene,
+        return launch_camera(camera_light_kernel<kOutI32x4, KeepAll>,
+                             camera_light_kernel<kOutI32x4, CubeCull>, 16, ctx, camera,
+                             device_scene, device_accel, width, row_begin, row_end,
+                             device_reflectivity, depth, shadows, shared, device_out, stream);
+    return launch_camera(camera_light_kernel<kOutRgba8, KeepAll>,
+                         camera_light_kernel<kOutRgba8, CubeCull>, 4, ctx, camera, device_scene,
                          device_accel, width, row_begin, row_end, device_reflectivity, depth,
                          shadows, shared, device_out, stream);
 }

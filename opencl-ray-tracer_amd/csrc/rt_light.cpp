@@ -3,12 +3,11 @@
 // rt_reflect_hits / rt_light_hits_reflected and the two together,
 // rt_shadow_hits_reflected / rt_light_hits_shadowed_reflected, and the mirror
 // chain's rt_bounce_hits / rt_light_hits_mirrored, on the host, and
-// the argument check they share with the device entry points (the launch of
-// rt_light_device.inc, for rt_light.hip, rt_shadow.hip, rt_reflect.hip and
-// rt_shadow_reflect.hip; rt_mirror.hip's own).  One pixel loop, run() of
-// include/rt_light_run.h; each function is its
-// argument checks and the per-pixel call it hands to the loop.  Behind them the
-// ray queries, rt_cast_rays / rt_occlude_rays /
+// the argument checks they share with the device entry points (the launch of
+// rt_light_device.inc, for every kernel over a hit frame) and with the culled
+// and the camera calls (check_chain_settings, check_reflectivity).  One pixel
+// loop, run() of include/rt_light_run.h; each function is its argument checks
+// and the per-pixel call it hands to the loop.  Behind them the ray queries, rt_cast_rays / rt_occlude_rays /
 // rt_camera_rays / rt_cast_camera: the loops of include/rt_rays_run.h over the
 // unculled walks and the camera text of include/rt_rays_impl.h, and the checks
 // they share with rt_rays.hip.
@@ -30,6 +29,29 @@ int check(const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32
     if (rt_args::check_args(scene, width, row_end, row_begin, row_end, RT_FORMAT_I32X4))
         return RT_ERR_INVALID_ARG;
     if (scene->num_lights > 0 && !scene->lights) return RT_ERR_INVALID_ARG;
+    return RT_OK;
+}
+
+int check_chain_settings(const rt_scene* scene, const float* reflectivity, int32_t max_bounces,
+                         int32_t shadows, int32_t out_format) {
+    if (out_format != RT_FORMAT_I32X4 && out_format != RT_FORMAT_RGBA8) return RT_ERR_INVALID_ARG;
+    if (max_bounces < 0 || max_bounces > RT_MAX_BOUNCES) return RT_ERR_INVALID_ARG;
+    if (shadows != 0 && shadows != 1) return RT_ERR_INVALID_ARG;
+    // the array may be missing only where no slot of it can be read
+    if (!reflectivity && max_bounces > 0 && scene &&
+        static_cast<int64_t>(scene->num_cubes) + scene->num_spheres > 0)
+        return RT_ERR_INVALID_ARG;
+    return RT_OK;
+}
+
+int check_reflectivity(const rt_scene& scene, const float* reflectivity, bool& mirrors) {
+    const int64_t n_slots = static_cast<int64_t>(scene.num_cubes) + scene.num_spheres;
+    mirrors = false;
+    if (reflectivity)
+        for (int64_t i = 0; i < n_slots; ++i) {
+            if (!(reflectivity[i] >= 0.0f && reflectivity[i] <= 1.0f)) return RT_ERR_INVALID_ARG;
+            mirrors = mirrors || reflectivity[i] != 0.0f;
+        }
     return RT_OK;
 }
 
@@ -122,21 +144,11 @@ int rt_light_hits_mirrored(const rt_hit* hits, const rt_scene* scene, const floa
                            int32_t width, int32_t row_begin, int32_t row_end,
                            const float* reflectivity, int32_t max_bounces, int32_t shadows,
                            int32_t out_format, void* out) {
-    if (out_format != RT_FORMAT_I32X4 && out_format != RT_FORMAT_RGBA8) return RT_ERR_INVALID_ARG;
-    if (max_bounces < 0 || max_bounces > RT_MAX_BOUNCES) return RT_ERR_INVALID_ARG;
-    if (shadows != 0 && shadows != 1) return RT_ERR_INVALID_ARG;
-    const int rc = check(hits, scene, ray_dir, width, row_begin, row_end, out);
-    if (rc) return rc;
-    // the array: every value in [0, 1] wherever one is given (NaN is refused
-    // too); it may be missing only where no slot of it can be read
-    const int64_t n_slots = static_cast<int64_t>(scene->num_cubes) + scene->num_spheres;
-    if (!reflectivity && max_bounces > 0 && n_slots > 0) return RT_ERR_INVALID_ARG;
+    int rc = check_chain_settings(scene, reflectivity, max_bounces, shadows, out_format);
+    if (!rc) rc = check(hits, scene, ray_dir, width, row_begin, row_end, out);
     bool mirrors = false;
-    if (reflectivity)
-        for (int64_t i = 0; i < n_slots; ++i) {
-            if (!(reflectivity[i] >= 0.0f && reflectivity[i] <= 1.0f)) return RT_ERR_INVALID_ARG;
-            mirrors = mirrors || reflectivity[i] != 0.0f;
-        }
+    if (!rc) rc = check_reflectivity(*scene, reflectivity, mirrors);
+    if (rc) return rc;
     if (max_bounces == 0 || !mirrors)  // rt_light_hits' / rt_light_hits_shadowed's frame, no walk
         return shadows ? rt_light_hits_shadowed(hits, scene, ray_dir, width, row_begin, row_end,
                                                 out_format, out)

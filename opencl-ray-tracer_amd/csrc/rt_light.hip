@@ -70,16 +70,16 @@ extern "C" {
 int rt_hit_surfaces_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
                            const float ray_dir[4], int32_t width, int32_t row_begin,
                            int32_t row_end, rt_surface* device_out, void* stream) {
-    return launch(light_kernel<kOutSurface>, 16, false, ctx, device_hits, device_scene, ray_dir,
-                  width, row_begin, row_end, device_out, stream);
+    return launch(KeepAll{}, 0, light_kernel<kOutSurface>, 16, false, ctx, device_hits,
+                  device_scene, ray_dir, width, row_begin, row_end, device_out, stream);
 }
 
 int rt_light_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
                          const float ray_dir[4], int32_t width, int32_t row_begin,
                          int32_t row_end, int32_t out_format, void* device_out, void* stream) {
-    return launch_lit(light_kernel<kOutI32x4>, light_kernel<kOutRgba8>, out_format, ctx,
-                      device_hits, device_scene, ray_dir, width, row_begin, row_end, device_out,
-                      stream);
+    return launch_lit(KeepAll{}, 0, light_kernel<kOutI32x4>, light_kernel<kOutRgba8>, out_format,
+                      ctx, device_hits, device_scene, ray_dir, width, row_begin, row_end,
+                      device_out, stream);
 }
 
 }  // extern "C"

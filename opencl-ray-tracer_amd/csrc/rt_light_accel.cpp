@@ -3,7 +3,8 @@
 // rt_light.cpp's functions of the same names without `_accel`, word for word in
 // what they return: the same pixel loop (include/rt_light_run.h) over the same
 // pixel functions (include/rt_light_impl.h), which take the culled walks of
-// include/rt_accel_impl.h in place of the unculled ones.
+// include/rt_accel_impl.h in place of the unculled ones, behind the same
+// checks of the settings and the reflectivity array (rt_light.cpp).
 // Plain C++, no HIP; built with -ffp-contract=off like rt_light.cpp.
 #include "rt_accel_impl.h"
 #include "rt_hip.h"
@@ -56,21 +57,12 @@ int rt_light_hits_mirrored_accel(const rt_hit* hits, const rt_scene* scene,
                                  int32_t width, int32_t row_begin, int32_t row_end,
                                  const float* reflectivity, int32_t max_bounces, int32_t shadows,
                                  int32_t out_format, void* out) {
-    if (out_format != RT_FORMAT_I32X4 && out_format != RT_FORMAT_RGBA8) return RT_ERR_INVALID_ARG;
-    if (max_bounces < 0 || max_bounces > RT_MAX_BOUNCES) return RT_ERR_INVALID_ARG;
-    if (shadows != 0 && shadows != 1) return RT_ERR_INVALID_ARG;
-    const int rc =
-        check_light_accel(hits, scene, ray_dir, width, row_begin, row_end, false, accel, out);
-    if (rc) return rc;
-    // the array, as rt_light_hits_mirrored checks it
-    const int64_t n_slots = static_cast<int64_t>(scene->num_cubes) + scene->num_spheres;
-    if (!reflectivity && max_bounces > 0 && n_slots > 0) return RT_ERR_INVALID_ARG;
+    int rc = check_chain_settings(scene, reflectivity, max_bounces, shadows, out_format);
+    if (!rc)
+        rc = check_light_accel(hits, scene, ray_dir, width, row_begin, row_end, false, accel, out);
     bool mirrors = false;
-    if (reflectivity)
-        for (int64_t i = 0; i < n_slots; ++i) {
-            if (!(reflectivity[i] >= 0.0f && reflectivity[i] <= 1.0f)) return RT_ERR_INVALID_ARG;
-            mirrors = mirrors || reflectivity[i] != 0.0f;
-        }
+    if (!rc) rc = check_reflectivity(*scene, reflectivity, mirrors);
+    if (rc) return rc;
     const CulledWalks w{accel};
     if (max_bounces == 0 || !mirrors) {  // no bounce walk
         if (!shadows)  // rt_light_hits' frame: no walk at all

@@ -1,7 +1,8 @@
 // rt_light_device.inc -- what the kernels of the deferred light pass share
 // (DESIGN.md §3.1a-d): the pixel prologue, the wave-uniform surface step, the
 // shadow walk, the bounce walk, the lit store, and on the host the one launch
-// function and the preload helper.  Included once by every translation unit of
+// function of every entry point over a hit frame, culled ones included, and
+// the preload helper.  Included once by every translation unit of
 // the light pass and of the ray queries, in front of its kernels; not a
 // standalone translation unit.
 //
@@ -31,6 +32,7 @@
 
 #include <cstdint>
 #include <initializer_list>
+#include <type_traits>
 
 #define RT_LIGHT_FN __host__ __device__ inline
 #include "rt_hip.h"
@@ -212,41 +214,61 @@ __device__ __forceinline__ void store_lit(void* __restrict__ out, int64_t i, con
         reinterpret_cast<uint32_t*>(out)[i] = rt_light::pack_rgba8(px);
 }
 
-// The launch of every entry point.  `align`: of `out`, in bytes; `mask`: the
-// output holds one bit per light, so at most 32; `refl`: nothing, or the
-// reflectivity of a kernel that takes one (after the ray direction).
-template <typename Kernel, typename... Refl>
-int launch(Kernel kernel, uintptr_t align, bool mask, rt_ctx* ctx, const rt_hit* hits,
-           const rt_scene* scene, const float* ray_dir, int32_t width, int32_t row_begin,
-           int32_t row_end, void* out, void* stream, Refl... refl) {
+// What launch() refuses of a kernel's own arguments: a reflectivity outside
+// [0, 1] (NaN too), a misaligned reflectivity array.
+inline bool refused(float refl) { return !(refl >= 0.0f && refl <= 1.0f); }
+inline bool refused(const float* refl) { return reinterpret_cast<uintptr_t>(refl) % sizeof(float); }
+inline bool refused(int32_t) { return false; }
+
+// The launch of every entry point of a hit frame.  `cull`: KeepAll, for a
+// kernel that takes `out` second, or CubeCull{accel}, for one that takes the
+// records there and `out` last; `shared`: bytes of dynamic shared memory;
+// `align`: of `out`, in bytes; `mask`: the output holds one bit per light, so
+// at most 32; `own`: the kernel's own arguments between the ray direction and
+// the scene: nothing, one reflectivity, or the chain's array, depth and
+// shadows.  Every check runs before any HIP call.
+template <typename Cull, typename Kernel, typename... Own>
+int launch(Cull cull, size_t shared, Kernel kernel, uintptr_t align, bool mask, rt_ctx* ctx,
+           const rt_hit* hits, const rt_scene* scene, const float* ray_dir, int32_t width,
+           int32_t row_begin, int32_t row_end, void* out, void* stream, Own... own) {
+    constexpr bool kCulled = !std::is_same_v<Cull, KeepAll>;
     if (!ctx || rt_light::check(hits, scene, ray_dir, width, row_begin, row_end, out) ||
         reinterpret_cast<uintptr_t>(hits) % sizeof(rt_hit) ||
         reinterpret_cast<uintptr_t>(out) % align)
         return RT_ERR_INVALID_ARG;
-    if ((!(refl >= 0.0f && refl <= 1.0f) || ...)) return RT_ERR_INVALID_ARG;  // NaN too
+    if ((refused(own) || ...)) return RT_ERR_INVALID_ARG;
     if (mask && scene->num_lights > 32) return RT_ERR_UNSUPPORTED;
     const int64_t n = (int64_t)(row_end - row_begin) * width;
     const int64_t blocks = (n + 255) / 256;
     if (blocks > INT32_MAX) return RT_ERR_UNSUPPORTED;
+    if (check_cull(scene, cull)) return RT_ERR_INVALID_ARG;
     if (hipSetDevice(rt_internal::ctx_device(ctx)) != hipSuccess) return RT_ERR_HIP;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : rt_internal::ctx_stream(ctx);
     if (!st) return RT_ERR_HIP;
-    kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(hits, out, n, width, row_begin, ray_dir[0],
-                                                         ray_dir[1], ray_dir[2], refl..., *scene);
+    const auto enqueue = [&](auto second, auto... last) {
+        kernel<<<dim3((unsigned)blocks), dim3(256), shared, st>>>(
+            hits, second, n, width, row_begin, ray_dir[0], ray_dir[1], ray_dir[2], own..., *scene,
+            last...);
+    };
+    if constexpr (kCulled)
+        enqueue(cull.accel, out);
+    else
+        enqueue(out);
     return hipGetLastError() == hipSuccess ? RT_OK : RT_ERR_HIP;
 }
 
 // The lit entry points: the int32x4 or the RGBA8 instance by `out_format`.
-template <typename Kernel, typename... Refl>
-int launch_lit(Kernel i32x4, Kernel rgba8, int32_t out_format, rt_ctx* ctx, const rt_hit* hits,
-               const rt_scene* scene, const float* ray_dir, int32_t width, int32_t row_begin,
-               int32_t row_end, void* out, void* stream, Refl... refl) {
+template <typename Cull, typename Kernel, typename... Own>
+int launch_lit(Cull cull, size_t shared, Kernel i32x4, Kernel rgba8, int32_t out_format,
+               rt_ctx* ctx, const rt_hit* hits, const rt_scene* scene, const float* ray_dir,
+               int32_t width, int32_t row_begin, int32_t row_end, void* out, void* stream,
+               Own... own) {
     if (out_format == RT_FORMAT_I32X4)
-        return launch(i32x4, 16, false, ctx, hits, scene, ray_dir, width, row_begin, row_end, out,
-                      stream, refl...);
+        return launch(cull, shared, i32x4, 16, false, ctx, hits, scene, ray_dir, width, row_begin,
+                      row_end, out, stream, own...);
     if (out_format == RT_FORMAT_RGBA8)
-        return launch(rgba8, 4, false, ctx, hits, scene, ray_dir, width, row_begin, row_end, out,
-                      stream, refl...);
+        return launch(cull, shared, rgba8, 4, false, ctx, hits, scene, ray_dir, width, row_begin,
+                      row_end, out, stream, own...);
     return RT_ERR_INVALID_ARG;
 }
 

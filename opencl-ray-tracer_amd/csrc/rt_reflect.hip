@@ -74,8 +74,8 @@ extern "C" {
 int rt_reflect_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
                            const float ray_dir[4], int32_t width, int32_t row_begin,
                            int32_t row_end, rt_hit* device_out, void* stream) {
-    return launch(reflect_kernel<kOutBounce>, 8, false, ctx, device_hits, device_scene, ray_dir,
-                  width, row_begin, row_end, device_out, stream, 0.0f);
+    return launch(KeepAll{}, 0, reflect_kernel<kOutBounce>, 8, false, ctx, device_hits,
+                  device_scene, ray_dir, width, row_begin, row_end, device_out, stream, 0.0f);
 }
 
 int rt_light_hits_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
@@ -83,9 +83,9 @@ int rt_light_hits_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
                                    int32_t width, int32_t row_begin, int32_t row_end,
                                    float reflectivity, int32_t out_format, void* device_out,
                                    void* stream) {
-    return launch_lit(reflect_kernel<kOutI32x4>, reflect_kernel<kOutRgba8>, out_format, ctx,
-                      device_hits, device_scene, ray_dir, width, row_begin, row_end, device_out,
-                      stream, reflectivity);
+    return launch_lit(KeepAll{}, 0, reflect_kernel<kOutI32x4>, reflect_kernel<kOutRgba8>,
+                      out_format, ctx, device_hits, device_scene, ray_dir, width, row_begin,
+                      row_end, device_out, stream, reflectivity);
 }
 
 }  // extern "C"

@@ -3,7 +3,10 @@
 //
 // One kernel template over the output (mask, int32x4, RGBA8): the pixel
 // prologue, the surface step, the shadow walk at the hit point, one 4- or
-// 16-byte store.  No workspace, one launch.
+// 16-byte store.  No workspace, one launch.  (shadow_accel_kernel of
+// rt_shadow_accel.hip is the mask form over CubeCull.  One body for both was
+// one instruction shorter in the mask form and missed the timing rule on one
+// line, so each keeps its text: profiles/chain_shared/README.md.)
 //
 // The walk is what the kernel costs: lights x (12 * cubes + spheres) tests
 // per pixel, each triangle test in fp64.  A lane takes part only while it is
@@ -63,17 +66,17 @@ extern "C" {
 int rt_shadow_hits_device(rt_ctx* ctx, const rt_hit* device_hits, const rt_scene* device_scene,
                           const float ray_dir[4], int32_t width, int32_t row_begin,
                           int32_t row_end, uint32_t* device_out, void* stream) {
-    return launch(shadow_kernel<kOutMask>, 4, true, ctx, device_hits, device_scene, ray_dir, width,
-                  row_begin, row_end, device_out, stream);
+    return launch(KeepAll{}, 0, shadow_kernel<kOutMask>, 4, true, ctx, device_hits, device_scene,
+                  ray_dir, width, row_begin, row_end, device_out, stream);
 }
 
 int rt_light_hits_shadowed_device(rt_ctx* ctx, const rt_hit* device_hits,
                                   const rt_scene* device_scene, const float ray_dir[4],
                                   int32_t width, int32_t row_begin, int32_t row_end,
                                   int32_t out_format, void* device_out, void* stream) {
-    return launch_lit(shadow_kernel<kOutI32x4>, shadow_kernel<kOutRgba8>, out_format, ctx,
-                      device_hits, device_scene, ray_dir, width, row_begin, row_end, device_out,
-                      stream);
+    return launch_lit(KeepAll{}, 0, shadow_kernel<kOutI32x4>, shadow_kernel<kOutRgba8>,
+                      out_format, ctx, device_hits, device_scene, ray_dir, width, row_begin,
+                      row_end, device_out, stream);
 }
 
 }  // extern "C"

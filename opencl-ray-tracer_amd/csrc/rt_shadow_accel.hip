@@ -1,7 +1,7 @@
 // rt_shadow_accel.hip -- rt_shadow_hits_accel_device: the shadow mask of the
 // deferred light pass over the prebuilt cube records, on the device
-// (DESIGN.md §3.1h).  shadow_kernel's mask form (rt_shadow.hip) with
-// light_walk culled by CubeCull of rt_accel_impl.h: a lane tests
+// (DESIGN.md §3.1h).  shadow_kernel's mask form (rt_shadow.hip; each keeps its
+// text, profiles/chain_shared/README.md) with light_walk culled by CubeCull of rt_accel_impl.h: a lane tests
 // a cube for a light only where the cube is not its own and the keep test of
 // include/rt_accel_impl.h keeps it for the lane's segment to that light.  The
 // mask is rt_shadow_hits_device's word for word.
@@ -27,7 +27,7 @@ using rt_light::CubeCull;
 __global__ void __launch_bounds__(256)
 shadow_accel_kernel(const rt_hit* __restrict__ hits, const rt_cube_bound* __restrict__ accel,
                     int64_t n, int32_t width, int32_t row_begin, float dx, float dy, float dz,
-                    rt_scene s, uint32_t* __restrict__ out) {
+                    rt_scene s, void* __restrict__ out) {
     using rt_light::Vec3;
     const int64_t i = pixel_index();
     if (i >= n) return;
@@ -46,37 +46,19 @@ shadow_accel_kernel(const rt_hit* __restrict__ hits, const rt_cube_bound* __rest
         }
         light_walk<true>(s, p, nrm, obj, hit, mask, CubeCull{accel});
     }
-    out[i] = mask;
+    reinterpret_cast<uint32_t*>(out)[i] = mask;
 }
 
 }  // namespace
 
 extern "C" {
 
-// launch() of rt_light_device.inc for the mask, with the record and its check
-// behind the unculled call's; every check runs before any HIP call.
 int rt_shadow_hits_accel_device(rt_ctx* ctx, const rt_hit* device_hits,
                                 const rt_scene* device_scene, const rt_cube_bound* device_accel,
                                 const float ray_dir[4], int32_t width, int32_t row_begin,
                                 int32_t row_end, uint32_t* device_out, void* stream) {
-    if (!ctx ||
-        rt_light::check(device_hits, device_scene, ray_dir, width, row_begin, row_end,
-                        device_out) ||
-        reinterpret_cast<uintptr_t>(device_hits) % sizeof(rt_hit) ||
-        reinterpret_cast<uintptr_t>(device_out) % 4)
-        return RT_ERR_INVALID_ARG;
-    if (device_scene->num_lights > 32) return RT_ERR_UNSUPPORTED;  // one bit per light
-    const int64_t n = (int64_t)(row_end - row_begin) * width;
-    const int64_t blocks = (n + 255) / 256;
-    if (blocks > INT32_MAX) return RT_ERR_UNSUPPORTED;
-    if (rt_light::check_accel(device_scene, device_accel)) return RT_ERR_INVALID_ARG;
-    if (hipSetDevice(rt_internal::ctx_device(ctx)) != hipSuccess) return RT_ERR_HIP;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : rt_internal::ctx_stream(ctx);
-    if (!st) return RT_ERR_HIP;
-    shadow_accel_kernel<<<dim3((unsigned)blocks), dim3(256), 0, st>>>(
-        device_hits, device_accel, n, width, row_begin, ray_dir[0], ray_dir[1], ray_dir[2],
-        *device_scene, device_out);
-    return hipGetLastError() == hipSuccess ? RT_OK : RT_ERR_HIP;
+    return launch(CubeCull{device_accel}, 0, shadow_accel_kernel, 4, true, ctx, device_hits,
+                  device_scene, ray_dir, width, row_begin, row_end, device_out, stream);
 }
 
 }  // extern "C"

@@ -118,8 +118,8 @@ int rt_shadow_hits_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
                                     const rt_scene* device_scene, const float ray_dir[4],
                                     int32_t width, int32_t row_begin, int32_t row_end,
                                     uint32_t* device_out, void* stream) {
-    return launch(shadow_reflect_kernel<kOutMask2>, 4, true, ctx, device_hits, device_scene,
-                  ray_dir, width, row_begin, row_end, device_out, stream, 0.0f);
+    return launch(KeepAll{}, 0, shadow_reflect_kernel<kOutMask2>, 4, true, ctx, device_hits,
+                  device_scene, ray_dir, width, row_begin, row_end, device_out, stream, 0.0f);
 }
 
 int rt_light_hits_shadowed_reflected_device(rt_ctx* ctx, const rt_hit* device_hits,
@@ -127,9 +127,10 @@ int rt_light_hits_shadowed_reflected_device(rt_ctx* ctx, const rt_hit* device_hi
                                             int32_t width, int32_t row_begin, int32_t row_end,
                                             float reflectivity, int32_t out_format,
                                             void* device_out, void* stream) {
-    return launch_lit(shadow_reflect_kernel<kOutI32x4>, shadow_reflect_kernel<kOutRgba8>,
-                      out_format, ctx, device_hits, device_scene, ray_dir, width, row_begin,
-                      row_end, device_out, stream, reflectivity);
+    return launch_lit(KeepAll{}, 0, shadow_reflect_kernel<kOutI32x4>,
+                      shadow_reflect_kernel<kOutRgba8>, out_format, ctx, device_hits,
+                      device_scene, ray_dir, width, row_begin, row_end, device_out, stream,
+                      reflectivity);
 }
 
 }  // extern "C"
