@@ -244,7 +244,10 @@ int enqueue_verdict_copy(rt_ctx* ctx, hipStream_t stream) {
 #define RT_NT_WIDE 7
 #endif
 #ifndef RT_ROWS_NARROW
-#define RT_ROWS_NARROW 4  // pixels per lane in the 16x16 build (A/B variants: 8 = 16x32 tiles)
+#define RT_ROWS_NARROW 4  // pixels per lane in the 16x16 build.  8 (16x32 tiles) still builds, but
+                          // its trace3_kernel spills some 200 VGPRs: the code that kept an 8-row
+                          // walk in 64 VGPRs was rejected and removed (last in
+                          // 96b3fb5)
 #endif
 #define RT_TILE_W RT_TILE_NARROW
 #define RT_NT_STORES RT_NT_NARROW

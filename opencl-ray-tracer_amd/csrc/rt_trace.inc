@@ -20,6 +20,9 @@
     defined(RT_PREP_TRIDEPTH) || defined(RT_PREP_OVERDRAW) || defined(RT_DEPTH_CULL)
 #error "RT_WALK_BALLOT, RT_WALK_BALLOT_SPLIT, RT_BIN_ABLATE, RT_EXTRA_VALU, RT_EXTRA_SALU, RT_REC_U32, RT_PREP_TRIDEPTH, RT_PREP_OVERDRAW and RT_DEPTH_CULL were decided and removed (DESIGN.md §3.5); their code is in history, last at commit 9cad428"
 #endif
+#if defined(RT_RECOMPUTE_XY) || defined(RT_ROW_GROUP)
+#error "RT_RECOMPUTE_XY and RT_ROW_GROUP (the 8-rows-per-lane trace3_kernel) were decided and removed (DESIGN.md §3.5); their code is in history, last at commit 96b3fb5"
+#endif
 namespace {
 
 // Build-time geometry / feature knobs (A/B variants: scripts/variants.sh).
@@ -798,27 +801,8 @@ __device__ __forceinline__ float tri_row(const TriRec& r, double px, double py, 
     return (float)t;
 }
 
-// A lane's pixel coordinates for one candidate test.  kRecomputeXY: re-derived
-// from pixel 0 at each use (exact adds of small integers, in asm volatile so
-// they are neither hoisted out of the walk nor kept live across it) instead
-// of held in 2 x kRowsPerLane f64 + f32 registers for the whole walk: what
-// lets a build of 8 rows per lane fit 64 VGPRs (8 waves per SIMD).  The
-// values are the same exact integers either way, so results are unchanged.
-#ifndef RT_RECOMPUTE_XY
-#define RT_RECOMPUTE_XY (RT_ROWS > 4)
-#endif
-constexpr bool kRecomputeXY = RT_RECOMPUTE_XY != 0;
-
-__device__ __forceinline__ double add_f64_fresh(double a, double b) {
-    double r;
-    asm volatile("v_add_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b));
-    return r;
-}
-__device__ __forceinline__ float add_f32_fresh(float a, float b) {
-    float r;
-    asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "s"(b), "v"(a));
-    return r;
-}
+// The rows of a lane for one triangle: its pixel coordinates are held in
+// px / py (exact integers) for the whole walk.
 __device__ __forceinline__ void tri_rows(const TriRec& r, unsigned bits, const double* px,
                                          const double* py, float* t) {
     bool pass;
@@ -897,79 +881,6 @@ __device__ __forceinline__ void sph_rows(const SphRec& s, unsigned bits, const f
 #pragma unroll
     for (int j = 0; j < kRowsPerLane; ++j)  // t0 == 0 never takes; block kept (uniform)
         t[j] = (t[j] != 0.0f) && ((bits >> (2 * row_block(j))) & 1u) ? t[j] : __builtin_nanf("");
-}
-
-// The fresh-coordinate forms (kRecomputeXY) of tri_rows / sph_rows: rows in
-// groups of kRowGroup, each group's coordinates re-derived from pixel 0 and
-// its results fenced (asm volatile) before the next group's coordinates, so
-// at most one group's temporaries are live at a time.  Same operations on
-// the same values as tri_rows / sph_rows (one tile verdict, kBlocks == 1).
-#ifndef RT_ROW_GROUP
-#define RT_ROW_GROUP 4
-#endif
-constexpr int kRowGroup = kRowsPerLane < RT_ROW_GROUP ? kRowsPerLane : RT_ROW_GROUP;
-__device__ __forceinline__ void fence_rows(float* t, int j0) {
-#pragma unroll
-    for (int i = 0; i < kRowGroup; ++i) asm volatile("" : "+v"(t[j0 + i]));
-}
-
-__device__ __forceinline__ void tri_rows_fresh(const TriRec& r, unsigned bits, double px0,
-                                               double py0, float* t) {
-    static_assert(kBlocks == 1, "fresh coordinates: whole-tile verdicts");
-    bool pass;
-#pragma unroll
-    for (int g = 0; g < kRowsPerLane; g += kRowGroup) {
-        double qx[kRowGroup], qy[kRowGroup];
-#pragma unroll
-        for (int i = 0; i < kRowGroup; ++i) {
-            const int j = g + i;
-            qx[i] = pix_dx(j) ? add_f64_fresh(px0, (double)pix_dx(j)) : px0;
-            qy[i] = pix_dy(j) ? add_f64_fresh(py0, (double)pix_dy(j)) : py0;
-        }
-        if (bits & 2u) {
-#pragma unroll
-            for (int i = 0; i < kRowGroup; ++i)
-                t[g + i] = tri_row(r, qx[i], qy[i], false, &pass);
-        } else {
-#pragma unroll
-            for (int i = 0; i < kRowGroup; ++i) {
-                const float tf = tri_row(r, qx[i], qy[i], true, &pass);
-                t[g + i] = pass ? tf : __builtin_nanf("");
-            }
-        }
-        fence_rows(t, g);
-    }
-}
-
-__device__ __forceinline__ void sph_rows_fresh(const SphRec& s, unsigned bits, float px0,
-                                               float py0, float* t) {
-#pragma unroll
-    for (int g = 0; g < kRowsPerLane; g += kRowGroup) {
-        float arg[kRowGroup];
-#pragma unroll
-        for (int i = 0; i < kRowGroup; ++i) {
-            const int j = g + i;
-            const float qx = pix_dx(j) ? add_f32_fresh(px0, (float)pix_dx(j)) : px0;
-            const float qy = pix_dy(j) ? add_f32_fresh(py0, (float)pix_dy(j)) : py0;
-            const float lx = s.cx - qx;
-            const float lx2 = lx * lx;
-            const float ly = s.cy - qy;
-            const float a = lx2 + ly * ly;
-            const float dist2 = (a + s.kzw) - s.tca2;
-            arg[i] = s.r2 - dist2;
-        }
-        if (!(s.fast != 0.0f)) {
-#pragma unroll
-            for (int i = 0; i < kRowGroup; ++i) t[g + i] = s.tca - sqrtf(arg[i]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < kRowGroup; ++i) t[g + i] = s.tca - sqrt_rn_normal(arg[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < kRowGroup; ++i)
-            t[g + i] = (t[g + i] != 0.0f) && (bits & 1u) ? t[g + i] : __builtin_nanf("");
-        fence_rows(t, g);
-    }
 }
 
 // Tile classification of one candidate against the rectangle
@@ -1772,6 +1683,93 @@ __device__ __forceinline__ unsigned wave_max_key(const float* closest) {
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// What the five tile kernels below (trace3_kernel, trace3_split_kernel,
+// trace_small_kernel, trace_bin_kernel, frame_small_kernel) have in common,
+// as preprocessor text: the compiler gets the same tokens at the same place
+// as from a copy in each kernel, so every kernel's instruction stream is what
+// it was with the copies (profiles/walk_shared/).  As __forceinline__
+// functions, in seven wordings, none of the three was codegen-neutral in
+// these kernels at the 64-VGPR ceiling (DESIGN.md §3.5).  #undef first: this
+// file is compiled once per tile build.
+
+// Non-finite scene data: the reference algorithm verbatim for the lane's
+// pixels (generic_kernel's collide_generic), one row at a time.  Which waves
+// run it, and on what condition, is each kernel's own.
+// Expects in scope: x, y0, width, row_begin, row_end, scene, dir, out, kFmt.
+#undef RT_REFERENCE_PIXELS
+#define RT_REFERENCE_PIXELS()                                                            \
+    _Pragma("unroll 1") for (int j = 0; j < kRowsPerLane; ++j) {                         \
+        const int xj = x + pix_dx(j), y = y0 + pix_dy(j);                                \
+        if (xj < width && y < row_end)                                                   \
+            store_fmt<kFmt>(                                                             \
+                out, (int64_t)(y - row_begin) * width + xj,                              \
+                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f), \
+                                      dir));                                             \
+    }
+
+// A lane's state for the walk: nothing hit yet, and the coordinates of its
+// kRowsPerLane pixels (exact integers) as tri_rows and sph_rows take them.
+// Expects in scope: x, y0 (the lane's pixel 0), and the arrays closest, hit,
+// px, py, pxf, pyf, declared by the kernel.
+#undef RT_INIT_ROWS
+#define RT_INIT_ROWS()                                             \
+    _Pragma("unroll") for (int j = 0; j < kRowsPerLane; ++j) {     \
+        closest[j] = kFar;                                         \
+        hit[j] = -1;                                               \
+        py[j] = (double)(y0 + pix_dy(j));                          \
+        pyf[j] = (float)(y0 + pix_dy(j));                          \
+        px[j] = (double)(x + pix_dx(j));                           \
+        pxf[j] = (float)(x + pix_dx(j));                           \
+    }
+
+// The record declarations of the candidate step.  From memory: scalar loads,
+// three of the triangle's fields pinned in SGPRs.  From frame_small_kernel's
+// LDS (s_tri, s_sph): broadcast LDS reads, used as VGPR operands (moving them
+// to SGPRs, one v_readfirstlane per dword, measured slower).
+#undef RT_TRI_MEM
+#define RT_TRI_MEM                   \
+    const TriRec r = tri_at(tri, p); \
+    asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz))
+#undef RT_SPH_MEM
+#define RT_SPH_MEM const SphRec r = sph_at(sph, p - n_tri)
+#undef RT_TRI_LDS
+#define RT_TRI_LDS const TriRec& r = s_tri[p]
+#undef RT_SPH_LDS
+#define RT_SPH_LDS const SphRec& r = s_sph[p - n_tri]
+
+// One kept candidate p (tile bits `bits`) against the lane's rows.  Both
+// branches produce t per row (NaN: may not take); closest and hit are updated
+// once, after them (round 4: trace 1-3 % faster than a test-and-update in
+// each branch, DESIGN.md §3.5).  A sphere whose lower bound no lane's closest
+// exceeds is skipped: t0 >= tmin >= every closest, so no lane can take it
+// (strict <); the bound is refreshed only when a candidate was tested since.
+// It `continue`s on such a sphere, so it stands directly inside the walk's
+// loop, not in a nested one.
+// TRI, SPH: the declaration of the record `r` (one pair above).  N_CUBES: the
+// cube count as the kernel has it (an argument or scene.n_cubes: which SGPR).
+// Expects in scope: p, bits, n_tri, px, py, pxf, pyf, closest, hit,
+// tile_max_key, dirty.
+#undef RT_TEST_CANDIDATE
+#define RT_TEST_CANDIDATE(TRI, SPH, N_CUBES)              \
+    float tc[kRowsPerLane];                               \
+    int slot;                                             \
+    if (p < n_tri) {                                      \
+        TRI;                                              \
+        tri_rows(r, bits, px, py, tc);                    \
+        slot = p / 12;                                    \
+    } else {                                              \
+        SPH;                                              \
+        if (dirty) {                                      \
+            tile_max_key = wave_max_key(closest);         \
+            dirty = false;                                \
+        }                                                 \
+        if (r.tmin_key >= tile_max_key) continue;         \
+        sph_rows(r, bits, pxf, pyf, tc);                  \
+        slot = (N_CUBES) + (p - n_tri);                   \
+    }                                                     \
+    take_rows(tc, slot, closest, hit);                    \
+    dirty = true
+
 // One wave (= one workgroup) per kWaveTile x kWaveTileH tile, all candidate
 // data on scalar loads: count, then ids and tile words 8 at a time, then the
 // records of the candidates this tile keeps (in the reference's primitive
@@ -1826,29 +1824,14 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_kernel(
     const int count_raw = kMode == 1 ? 0 : counts[cb];
     if (tile_in && kMode == 0 && count_raw < 0) {
         // Non-finite scene data: run the reference algorithm verbatim.
-#pragma unroll 1
-        for (int j = 0; j < kRowsPerLane; ++j) {
-            const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
-            if (xj < width && y < row_end)
-                store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
-                                                dir));
-        }
+        RT_REFERENCE_PIXELS()
     } else if (tile_in) {
         int4v pix[kRowsPerLane];  // assigned after the walk (not live during it)
         float closest[kRowsPerLane];
         int hit[kRowsPerLane];
         double px[kRowsPerLane], py[kRowsPerLane];
         float pxf[kRowsPerLane], pyf[kRowsPerLane];
-#pragma unroll
-        for (int j = 0; j < kRowsPerLane; ++j) {
-            closest[j] = kFar;
-            hit[j] = -1;
-            py[j] = (double)(y0 + pix_dy(j));
-            pyf[j] = (float)(y0 + pix_dy(j));
-            px[j] = (double)(x + pix_dx(j));
-            pxf[j] = (float)(x + pix_dx(j));
-        }
+        RT_INIT_ROWS()
         // order_key of the largest `closest` in the tile, refreshed lazily
         unsigned tile_max_key = order_key(kFar);
         bool dirty = false;
@@ -1877,35 +1860,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace3_kernel(
                     hit[0] = hit[0] > p ? hit[0] : -1;
                     continue;
                 }
-                // both branches produce t per row (NaN: may not take); closest
-                // and hit are updated once, after them (round 4: trace 1-3 %
-                // faster than a test-and-update in each branch, DESIGN.md §3.5)
-                float tc[kRowsPerLane];
-                int slot;
-                if (p < n_tri) {
-                    const TriRec r = tri_at(tri, p);
-                    asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-                    if constexpr (kRecomputeXY)
-                        tri_rows_fresh(r, bits, px[0], py[0], tc);
-                    else
-                        tri_rows(r, bits, px, py, tc);
-                    slot = p / 12;
-                } else {
-                    const SphRec r = sph_at(sph, p - n_tri);
-                    // t0 >= tmin >= every closest: no lane can take it (strict <)
-                    if (dirty) {
-                        tile_max_key = wave_max_key(closest);
-                        dirty = false;
-                    }
-                    if (r.tmin_key >= tile_max_key) continue;
-                    if constexpr (kRecomputeXY)
-                        sph_rows_fresh(r, bits, pxf[0], pyf[0], tc);
-                    else
-                        sph_rows(r, bits, pxf, pyf, tc);
-                    slot = n_cubes + (p - n_tri);
-                }
-                take_rows(tc, slot, closest, hit);
-                dirty = true;
+                RT_TEST_CANDIDATE(RT_TRI_MEM, RT_SPH_MEM, n_cubes);
             }
         }
 #if RT_TIMELINE
@@ -1972,29 +1927,14 @@ __global__ void __launch_bounds__(64 * kSplitMax) RT_TRACE_ATTR trace3_split_ker
     const int count_raw = counts[cb];
     if (count_raw < 0) {  // non-finite scene data: the reference verbatim (wave 0)
         if (wave != 0) return;
-#pragma unroll 1
-        for (int j = 0; j < kRowsPerLane; ++j) {
-            const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
-            if (xj < width && y < row_end)
-                store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
-                                                dir));
-        }
+        RT_REFERENCE_PIXELS()
         return;
     }
     float closest[kRowsPerLane];
     int hit[kRowsPerLane];
     double px[kRowsPerLane], py[kRowsPerLane];
     float pxf[kRowsPerLane], pyf[kRowsPerLane];
-#pragma unroll
-    for (int j = 0; j < kRowsPerLane; ++j) {
-        closest[j] = kFar;
-        hit[j] = -1;
-        py[j] = (double)(y0 + pix_dy(j));
-        pyf[j] = (float)(y0 + pix_dy(j));
-        px[j] = (double)(x + pix_dx(j));
-        pxf[j] = (float)(x + pix_dx(j));
-    }
+    RT_INIT_ROWS()
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
     const int* __restrict__ ids = lists + (int64_t)cb * kListStride * half_cap;
@@ -2022,25 +1962,7 @@ __global__ void __launch_bounds__(64 * kSplitMax) RT_TRACE_ATTR trace3_split_ker
             if (!mine) continue;
             const int p = __builtin_amdgcn_readlane(idl, k);
             const unsigned bits = (unsigned)__builtin_amdgcn_readlane((int)bl, k);
-            float tc[kRowsPerLane];
-            int slot;
-            if (p < n_tri) {
-                const TriRec r = tri_at(tri, p);
-                asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-                tri_rows(r, bits, px, py, tc);
-                slot = p / 12;
-            } else {
-                const SphRec r = sph_at(sph, p - n_tri);
-                if (dirty) {
-                    tile_max_key = wave_max_key(closest);
-                    dirty = false;
-                }
-                if (r.tmin_key >= tile_max_key) continue;
-                sph_rows(r, bits, pxf, pyf, tc);
-                slot = scene.n_cubes + (p - n_tri);
-            }
-            take_rows(tc, slot, closest, hit);
-            dirty = true;
+            RT_TEST_CANDIDATE(RT_TRI_MEM, RT_SPH_MEM, scene.n_cubes);
         }
     }
     // merge into wave 0: the other waves' closest / hit through LDS
@@ -2126,15 +2048,8 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
                                : 0ull;
     const bool nonfinite = *nonfinite_flag == gen;
     int4v pix[kRowsPerLane];
-    if (nonfinite) {  // the reference algorithm verbatim (see trace3_kernel)
-#pragma unroll 1
-        for (int j = 0; j < kRowsPerLane; ++j) {
-            const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
-            if (xj < width && y < row_end)
-                store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
-                                                dir));
-        }
+    if (nonfinite) {  // the reference algorithm verbatim
+        RT_REFERENCE_PIXELS()
         return;
     }
     // lane i: candidate 64 c + i against this tile (coarse3_kernel's test).
@@ -2167,15 +2082,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
     int hit[kRowsPerLane];
     double px[kRowsPerLane], py[kRowsPerLane];
     float pxf[kRowsPerLane], pyf[kRowsPerLane];
-#pragma unroll
-    for (int j = 0; j < kRowsPerLane; ++j) {
-        closest[j] = kFar;
-        hit[j] = -1;
-        py[j] = (double)(y0 + pix_dy(j));
-        pyf[j] = (float)(y0 + pix_dy(j));
-        px[j] = (double)(x + pix_dx(j));
-        pxf[j] = (float)(x + pix_dx(j));
-    }
+    RT_INIT_ROWS()
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
 #pragma unroll
@@ -2185,25 +2092,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_small_kernel(
         keep[c] &= keep[c] - 1ull;
         const int p = 64 * c + b;
         const unsigned bits = ((inside[c] >> b) & 1ull) ? kTileMask : kKeepMask;
-        float tc[kRowsPerLane];  // one closest / hit update (as trace3_kernel)
-        int slot;
-        if (p < n_tri) {
-            const TriRec r = tri_at(tri, p);
-            asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-            tri_rows(r, bits, px, py, tc);
-            slot = p / 12;
-        } else {
-            const SphRec r = sph_at(sph, p - n_tri);
-            if (dirty) {
-                tile_max_key = wave_max_key(closest);
-                dirty = false;
-            }
-            if (r.tmin_key >= tile_max_key) continue;
-            sph_rows(r, bits, pxf, pyf, tc);
-            slot = n_cubes + (p - n_tri);
-        }
-        take_rows(tc, slot, closest, hit);
-        dirty = true;
+        RT_TEST_CANDIDATE(RT_TRI_MEM, RT_SPH_MEM, n_cubes);
     }
     shade_pixels<0, kFmt>(colours, closest, hit, pix);
     const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
@@ -2256,15 +2145,8 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
     const unsigned long long* rw = row_masks + (int64_t)cby * n_chunks;
     const unsigned long long* cw = col_masks + (int64_t)cbx * n_chunks;
     const bool nonfinite = *nonfinite_flag == gen;
-    if (nonfinite) {  // the reference algorithm verbatim (see trace3_kernel)
-#pragma unroll 1
-        for (int j = 0; j < kRowsPerLane; ++j) {
-            const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
-            if (xj < width && y < row_end)
-                store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
-                                                dir));
-        }
+    if (nonfinite) {  // the reference algorithm verbatim
+        RT_REFERENCE_PIXELS()
         return;
     }
     // (1) the bin's candidate ids in primitive order into LDS (launch() takes
@@ -2323,15 +2205,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
     int hit[kRowsPerLane];
     double px[kRowsPerLane], py[kRowsPerLane];
     float pxf[kRowsPerLane], pyf[kRowsPerLane];
-#pragma unroll
-    for (int j = 0; j < kRowsPerLane; ++j) {
-        closest[j] = kFar;
-        hit[j] = -1;
-        py[j] = (double)(y0 + pix_dy(j));
-        pyf[j] = (float)(y0 + pix_dy(j));
-        px[j] = (double)(x + pix_dx(j));
-        pxf[j] = (float)(x + pix_dx(j));
-    }
+    RT_INIT_ROWS()
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
     for (int i0 = 0; i0 < n_kept; i0 += 8) {
@@ -2343,25 +2217,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
             const int e = __builtin_amdgcn_readlane(ent, k);
             const int p = e & 0x7fffffff;
             const unsigned bits = e < 0 ? kTileMask : kKeepMask;
-            float tc[kRowsPerLane];
-            int slot;
-            if (p < n_tri) {
-                const TriRec r = tri_at(tri, p);
-                asm volatile("" ::"s"(r.p0), "s"(r.p1), "s"(r.dz));
-                tri_rows(r, bits, px, py, tc);
-                slot = p / 12;
-            } else {
-                const SphRec r = sph_at(sph, p - n_tri);
-                if (dirty) {
-                    tile_max_key = wave_max_key(closest);
-                    dirty = false;
-                }
-                if (r.tmin_key >= tile_max_key) continue;
-                sph_rows(r, bits, pxf, pyf, tc);
-                slot = scene.n_cubes + (p - n_tri);
-            }
-            take_rows(tc, slot, closest, hit);
-            dirty = true;
+            RT_TEST_CANDIDATE(RT_TRI_MEM, RT_SPH_MEM, scene.n_cubes);
         }
     }
     int4v pix[kRowsPerLane];
@@ -2381,7 +2237,7 @@ __global__ void __launch_bounds__(64) RT_TRACE_ATTR trace_bin_kernel(
 // with their records read from LDS, shades and stores.  No prep kernel, no
 // bin masks, no records in global memory: the frame is one launch with one
 // memory round trip (the scene) in front of the stores.  Non-finite scene
-// data: the reference algorithm verbatim, as trace3_kernel.
+// data: the reference algorithm verbatim (RT_REFERENCE_PIXELS).
 constexpr int kFusedWaves = RT_FUSED_WG;  // wave tiles (waves) per workgroup
 static_assert(kTiles % kFusedWaves == 0, "a workgroup's tiles lie in one bin");
 template <int kFmt, int kChunks>
@@ -2453,14 +2309,7 @@ __global__ void __launch_bounds__(64 * kFusedWaves) RT_FUSED_ATTR frame_small_ke
 #pragma unroll
     for (int c = 0; c < kPrepWaves; ++c) nonfinite |= s_bad[c] != 0u;
     if (nonfinite) {
-#pragma unroll 1
-        for (int j = 0; j < kRowsPerLane; ++j) {
-            const int xj = x + pix_dx(j), y = y0 + pix_dy(j);
-            if (xj < width && y < row_end)
-                store_fmt<kFmt>(out, (int64_t)(y - row_begin) * width + xj,
-                                collide_generic<kFmt>(scene, make_float4((float)xj, (float)y, 0.0f, 1.0f),
-                                                dir));
-        }
+        RT_REFERENCE_PIXELS()
         return;
     }
     unsigned long long keep[kChunks], inside[kChunks];
@@ -2481,15 +2330,7 @@ __global__ void __launch_bounds__(64 * kFusedWaves) RT_FUSED_ATTR frame_small_ke
     int hit[kRowsPerLane];
     double px[kRowsPerLane], py[kRowsPerLane];
     float pxf[kRowsPerLane], pyf[kRowsPerLane];
-#pragma unroll
-    for (int j = 0; j < kRowsPerLane; ++j) {
-        closest[j] = kFar;
-        hit[j] = -1;
-        py[j] = (double)(y0 + pix_dy(j));
-        pyf[j] = (float)(y0 + pix_dy(j));
-        px[j] = (double)(x + pix_dx(j));
-        pxf[j] = (float)(x + pix_dx(j));
-    }
+    RT_INIT_ROWS()
     unsigned tile_max_key = order_key(kFar);
     bool dirty = false;
 #pragma unroll
@@ -2499,32 +2340,22 @@ __global__ void __launch_bounds__(64 * kFusedWaves) RT_FUSED_ATTR frame_small_ke
         keep[c] &= keep[c] - 1ull;
         const int p = 64 * c + b;
         const unsigned bits = ((inside[c] >> b) & 1ull) ? kTileMask : kKeepMask;
-        float tc[kRowsPerLane];  // one closest / hit update (as trace3_kernel)
-        int slot;
-        if (p < n_tri) {
-            // broadcast LDS reads, used as VGPR operands (moving them to
-            // SGPRs, one v_readfirstlane per dword, measured slower)
-            const TriRec& r = s_tri[p];
-            tri_rows(r, bits, px, py, tc);
-            slot = p / 12;
-        } else {
-            const SphRec& r = s_sph[p - n_tri];
-            if (dirty) {
-                tile_max_key = wave_max_key(closest);
-                dirty = false;
-            }
-            if (r.tmin_key >= tile_max_key) continue;
-            sph_rows(r, bits, pxf, pyf, tc);
-            slot = scene.n_cubes + (p - n_tri);
-        }
-        take_rows(tc, slot, closest, hit);
-        dirty = true;
+        RT_TEST_CANDIDATE(RT_TRI_LDS, RT_SPH_LDS, scene.n_cubes);  // records from LDS
     }
     int4v pix[kRowsPerLane];
     shade_pixels<0, kFmt>(s_col, closest, hit, pix);
     const bool full = rel_x + kWaveTile <= width && tile_y + kWaveTileH <= row_end;
     store_rows<0, kFmt>(pix, rel_x, rel_y, lane, width, row_end - row_begin, full, out);
 }
+
+// the tile kernels' shared text ends here: none of it reaches the host half
+#undef RT_REFERENCE_PIXELS
+#undef RT_INIT_ROWS
+#undef RT_TRI_MEM
+#undef RT_SPH_MEM
+#undef RT_TRI_LDS
+#undef RT_SPH_LDS
+#undef RT_TEST_CANDIDATE
 
 }  // namespace
 

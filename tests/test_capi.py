@@ -55,17 +55,18 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 @pytest.mark.skipif(not Path(HIPCC).exists(), reason="needs hipcc")
-def test_removed_knob_stops_the_build():
+@pytest.mark.parametrize("knob", ["RT_WALK_BALLOT", "RT_RECOMPUTE_XY", "RT_ROW_GROUP"])
+def test_removed_knob_stops_the_build(knob):
     """A -D of a compile-time experiment that was decided and removed
     (rt_trace.inc's guard block) must not build the default unnoticed: the
     preprocessor stops and points at DESIGN.md.  Preprocessing only: no
     device, no code generation."""
     src = REPO / "opencl-ray-tracer_amd" / "csrc" / "rt_device.hip"
     r = subprocess.run([HIPCC, "-E", "--cuda-host-only", "-std=c++17", "-DRT_DIAG=0",
-                        "-DRT_WALK_BALLOT=1", "-I", str(REPO / "include"), "-o", os.devnull,
+                        "-D%s=1" % knob, "-I", str(REPO / "include"), "-o", os.devnull,
                         str(src)], capture_output=True, text=True, timeout=120)
     assert r.returncode != 0
-    assert "DESIGN.md" in r.stderr, r.stderr[-2000:]
+    assert "DESIGN.md" in r.stderr and knob in r.stderr, r.stderr[-2000:]
 
 
 def test_abi_version(pkg):
