@@ -8,9 +8,13 @@ a clear miss is (300000, -1).  Borderline and undecided rays are excluded and
 counted, and the counts are capped on the reference alone, before the library
 is called.
 
-What is left out, on purpose.  Bounces beyond the first: each level starts
-from a rounded point along a rounded direction, the errors compound, and no
-band derived here covers them.  The shadow segments and the first bounce are
+What is left out, on purpose.  Bounces beyond the first at curved or rotated
+mirrors: each level starts from a rounded point along a rounded direction, the
+errors compound, and no band derived here covers them.  Chains over flat,
+axis-aligned mirrors are judged, geometry and colour, by
+tests/test_exact_light.py: there every mirrored direction is exact in float32
+and each level starts from the float32 point of the library's own judged t, so
+nothing compounds.  The shadow segments and the first bounce are
 judged from the float32 hit point fl(o + t*d) itself, taken as an exact real:
 that is the segment the library is asked about, so no band is widened by the
 hit point's displacement.  That point is not read from the library, which
